@@ -1,11 +1,17 @@
 #!/usr/bin/env python
 """Headline benchmark: implicit time-steps/s of the 3-variable falling-film
-system (BASELINE config 3: M3, N = 1e6, periodic, upwind + ROS2) on MI355X,
-with the F+J stencil sweep priced against the HBM roofline and the reference's
-numpy-compiler path (CPU oracle) timed on the same box.
+system (BASELINE config 3: M3, N = 1e6, periodic, upwind + ROS2) on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
                   [--members-per-gpu M] [--scheme ROS2|RODASPR|Theta|BDF2] [--config 2|3|5]
+
+A plain run sets up, takes W warm-up steps, times exactly K steps, writes the
+state they computed if --dump-outputs is given, and prints one JSON line.
+--full adds everything else: the median of at least 25 timed K-step blocks,
+the F+J stencil sweep priced against the HBM roofline, the per-kernel
+breakdown, the rate through the Python scheme protocol, the reference's
+numpy-compiler path (CPU oracle) timed on the same box and the run's
+full-size parity against it, and on 8 ranks the BASELINE config 4 block.
 
 N > 1: launched by the driver through torch.distributed.run, one rank per GPU;
 every rank integrates its own members of the parameter sweep of BASELINE
@@ -219,6 +225,25 @@ def device_parity(ens, dt, nsteps, ref_uflat):
                         "full size, max-norm relative difference of the state")
 
 
+#: --dump-outputs writes at most this many bytes in all; above it, a fixed sample of the nodes
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, model, state, rank=0, world=1):
+    """The state after the last timed step, one float64 array [members][nodes] per dependent
+    variable, as ``outdir/<variable>.npy`` (``<variable>_rank<r>.npy`` on rank r of an N > 1 run).
+    Above DUMP_BYTES in all, every variable and member keeps the same seeded sample of nodes."""
+    nvar, nsys, N = state.shape
+    budget = DUMP_BYTES // max(world, 1)
+    if state.nbytes > budget:
+        k = budget // (8 * nvar * nsys)
+        state = state[:, :, np.sort(np.random.default_rng(0).choice(N, size=k, replace=False))]
+    os.makedirs(outdir, exist_ok=True)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    for name, arr in zip(model._dep_vars, state):
+        np.save(os.path.join(outdir, name + suffix + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
 def scheme_api_rate(model, cfg, N, scheme_name, dt, steps=20):
     """The same workload driven through the reference-style Python protocol
     ``t, fields = scheme(t, fields, dt, pars)`` with device-resident containers
@@ -254,21 +279,29 @@ def main():
     ap.add_argument("--repeats", type=int, default=0,
                     help="the timed K-step block is repeated this many times, each bracketed by "
                          "barrier + synchronize; value / ms_per_step are those of the median block.  "
-                         "0 (default): at least 25 blocks and at least 2500 steps in all, so that the "
-                         "GPU is busy for more than a second on the default workload")
+                         "0 (default): one block, exactly K timed steps; with --full at least 25 blocks "
+                         "and at least 2500 steps in all, so that the GPU is busy for more than a second "
+                         "on the default workload")
     ap.add_argument("--members-per-gpu", type=int, default=1)
     ap.add_argument("--config", type=int, default=3, choices=(2, 3, 5))
     ap.add_argument("--nodes", type=int, default=0, help="override N (default: BASELINE size)")
     ap.add_argument("--scheme", default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state of the last timed step as DIR/<variable>.npy (float64, "
+                         "[members][nodes]; a fixed sample of the nodes above %d MB in all)" % (DUMP_BYTES >> 20))
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the sweep kernel's roofline, the per-kernel "
+                         "pass, the Python-protocol rate, the CPU baseline and parity, the config 4 block")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline, no parity")
     ap.add_argument("--plain", action="store_true",
-                    help="only the timed loop (profiler runs): no per-kernel pass, no Python-protocol rate")
+                    help="with --full: only the timed loop (profiler runs): no per-kernel pass, "
+                         "no Python-protocol rate")
     ap.add_argument("--cpu-workers", type=int, default=0,
-                    help="also time the CPU baseline with this many member processes (ensemble runs)")
+                    help="with --full: also time the CPU baseline with this many member processes (ensemble runs)")
     args = ap.parse_args()
 
     if args.repeats <= 0:          # (a function of the arguments only: the same on every rank)
-        args.repeats = max(25, -(-2500 // max(args.steps, 1)))
+        args.repeats = max(25, -(-2500 // max(args.steps, 1))) if args.full else 1
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -322,8 +355,9 @@ def main():
     # HIP events (kernel begin/end timestamps) on the roofline kernel only, so the
     # timed region is not perturbed by instrumenting every launch of a step
     sweep_kernel = {"Theta": "tfk_sweep_fj_theta", "BDF2": "tfk_sweep_fj_bdf2"}.get(scheme, "tfk_sweep_fj")
-    solver.timing(kernels=[sweep_kernel])
-    solver.timing_reset()
+    if args.full:
+        solver.timing(kernels=[sweep_kernel])
+        solver.timing_reset()
     blocks = []
     # The film model's waves steepen: at dt = 1e-3 config 3 stays smooth for about 6000 steps
     # (tools/gpu_soak.py), after which the state itself blows up.  Runs longer than MAX_RUN_STEPS
@@ -346,11 +380,19 @@ def main():
             ens.step(dt)
         barrier()
         blocks.append(time.perf_counter() - t0)
-    sweep_ms, sweep_n = solver.timing_report().get(sweep_kernel, (0.0, 0))
-    solver.timing(False)
+    sweep_ms, sweep_n = 0.0, 0
+    if args.full:
+        sweep_ms, sweep_n = solver.timing_report().get(sweep_kernel, (0.0, 0))
+        solver.timing(False)
     ens.check()                                # a singular / unstable factorisation raises here
+    state = ens.state()                        # what the last timed step computed
+    if not np.isfinite(state).all():
+        raise RuntimeError("non-finite state after the timed steps")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, model, state, rank, world)
+    del state
     report, nprof = {}, 0
-    if not args.plain:
+    if args.full and not args.plain:
         # untimed pass with every launch instrumented: per-kernel breakdown
         if run_steps + 10 > MAX_RUN_STEPS:
             ens.restart()
@@ -375,9 +417,6 @@ def main():
         dist.all_gather_object(seen, dict(rank=rank, local_rank=local_rank, members=len(mine),
                                           device=_device_identity(torch, device_index),
                                           pid=os.getpid()))
-    state = ens.state()
-    if not np.isfinite(state).all():
-        raise RuntimeError("non-finite state after the timed steps")
 
     # BASELINE config 4 proper on the 8-GPU node: 64 members, member m on rank m % 8, 8 members per
     # rank through the same launches (the line's `value` stays the 1-member-per-GPU weak-scaling
@@ -386,7 +425,7 @@ def main():
     config4 = None
     want4 = (world == 8 and args.members_per_gpu == 1 and args.config == 3 and scheme == "ROS2"
              and not args.nodes) or os.environ.get("TRIFLOW_BENCH_CONFIG4") == "1"
-    if multi and want4:
+    if args.full and multi and want4:
         n4 = 8 * world
         table4 = member_table(n4, None) if rank == 0 else np.zeros((n4, 3))
         table4 = broadcast_table(table4)
@@ -440,7 +479,7 @@ def main():
         step_gbs = step_bytes / elapsed * args.steps / 1e9
         traffic, traffic_src = None, None
         tfile = os.path.join(ROOT, "profiles", "sweep_traffic.json")
-        if os.path.exists(tfile) and args.config == 3 and args.members_per_gpu == 1 \
+        if args.full and os.path.exists(tfile) and args.config == 3 and args.members_per_gpu == 1 \
                 and not args.nodes and scheme == "ROS2":
             with open(tfile) as f:
                 tj = json.load(f)
@@ -463,18 +502,20 @@ def main():
                        "members_per_gpu": args.members_per_gpu,
                        "parallelism": "ensemble members sharded by rank, no data-path collective",
                        "solver_levels": solver.describe()["chunks"]},
-            "roofline": {"bound": "hbm", "kernel": sweep_kernel,
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": bytes_per_launch,
-                         "avg_launch_ms": (sweep_ms / sweep_n) if sweep_n else None},
             "roofline_step": {"bound": "hbm", "achieved": step_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                               "frac": step_gbs / HBM_PEAK_GBS,
                               "algorithmic_bytes_per_step": step_bytes,
                               "formula": "SURVEY 8(d) implicit-step bytes: %d B/node" %
                                          step_bytes_per_node(model, scheme, stages)},
         }
+        if args.full:
+            # (HIP events on the sweep kernel during the timed steps)
+            out["roofline"] = {"bound": "hbm", "kernel": sweep_kernel,
+                               "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
+                               "traffic": traffic, "traffic_source": traffic_src,
+                               "algorithmic_bytes_per_launch": bytes_per_launch,
+                               "avg_launch_ms": (sweep_ms / sweep_n) if sweep_n else None}
         if fused and sweep_n:
             out["roofline"]["fused_bytes_per_launch"] = fused_bytes
             out["roofline"]["fused_frac"] = fused_bytes / (sweep_ms / sweep_n * 1e-3) / 1e9 / HBM_PEAK_GBS
@@ -500,7 +541,7 @@ def main():
                 workers = max(1, min(n4, os.cpu_count() or 1,
                                      int(psutil.virtual_memory().available // (6 << 30))))
                 config4["cpu_baseline_members"] = cpu_baseline(3, N, "ROS2", workers=workers)
-        if world == 1 and not args.plain and getattr(solver, "constant_jacobian", False):
+        if args.full and world == 1 and not args.plain and getattr(solver, "constant_jacobian", False):
             # a constant-matrix model (config 2) keeps its factorisation between steps; the reference
             # factorises in every step (schemes.py:148-149, 557): the same workload that way, so that
             # the two rates are never confused
@@ -525,10 +566,10 @@ def main():
                                              "note": "`value` above reuses the factorisation of the constant matrix "
                                                      "(tf_set_constant_jacobian); this is the rate with one "
                                                      "factorisation per step, as the reference does"}
-        if world == 1 and args.members_per_gpu == 1 and not args.plain:
+        if args.full and world == 1 and args.members_per_gpu == 1 and not args.plain:
             out["scheme_api_steps_per_s"] = scheme_api_rate(model, args.config, N, scheme, dt)
         parity_failed = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # member 0 of a one-member run is the BASELINE configuration itself: the oracle's
             # state after its timed steps pins the device state of this very run
             check = args.members_per_gpu == 1

@@ -670,8 +670,8 @@ def test_bench_process_group_one_rank():
                RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", HSA_ENABLE_IPC_MODE_LEGACY="0",
                TRIFLOW_BENCH_CONFIG4="1")
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--nodes", "20000",
-                          "--steps", "5", "--warmup", "2", "--repeats", "3", "--no-cpu-baseline", "--plain"],
-                         cwd=root, env=env, capture_output=True, text=True, timeout=600)
+                          "--steps", "5", "--warmup", "2", "--repeats", "3", "--full", "--no-cpu-baseline",
+                          "--plain"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     line = json.loads(res.stdout.strip().splitlines()[-1])
     assert line["backend"].startswith("nccl") and line["ranks_seen"] == 1 and len(line["devices_seen"]) == 1
@@ -694,7 +694,7 @@ def test_bench_two_ranks_rehearsal():
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", "29641", os.path.join(root, "bench.py"),
                           "--gpus", "2", "--nodes", "100000", "--steps", "5", "--warmup", "2", "--repeats", "3",
-                          "--no-cpu-baseline", "--plain"],
+                          "--full", "--no-cpu-baseline", "--plain"],
                          cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     line = json.loads([ln for ln in res.stdout.strip().splitlines() if ln.startswith("{")][-1])
@@ -713,7 +713,7 @@ def test_bench_line_carries_its_parity():
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--nodes", "20000",
-                          "--steps", "5", "--warmup", "2", "--repeats", "3", "--plain"],
+                          "--steps", "5", "--warmup", "2", "--repeats", "3", "--full", "--plain"],
                          cwd=root, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     line = json.loads(res.stdout.strip().splitlines()[-1])

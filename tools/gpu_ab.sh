@@ -9,7 +9,7 @@ for extra in "$@"; do
     i=$((i+1))
     echo "=== variant $i: [$extra]" | tee -a $OUT/summary.txt
     flags="${extra%%|*}"; envs=""; [[ "$extra" == *"|"* ]] && envs="${extra#*|}"
-    env TRIFLOW_HIPCC_EXTRA="$flags" $envs timeout -k 10 300 python3 bench.py --no-cpu-baseline --repeats 5 $ARGS > $OUT/v$i.json 2> $OUT/v$i.err || { echo "variant failed"; tail -5 $OUT/v$i.err; }
+    env TRIFLOW_HIPCC_EXTRA="$flags" $envs timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --repeats 5 $ARGS > $OUT/v$i.json 2> $OUT/v$i.err || { echo "variant failed"; tail -5 $OUT/v$i.err; }
     python3 - "$OUT/v$i.json" <<'PY' | tee -a $OUT/summary.txt
 import json, sys
 try:

@@ -11,7 +11,7 @@ stop_if_killed() { rc=$1; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "step
 if [ "$PART" = "1" ]; then
   timeout -k 10 900 python3 -m pytest tests -m gpu -q > $OUT/pytest.log 2>&1; rc=$?; tail -2 $OUT/pytest.log; stop_if_killed $rc
   timeout -k 10 200 python3 -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-  timeout -k 10 400 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err; stop_if_killed $?
+  timeout -k 10 400 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err; stop_if_killed $?
   timeout -k 10 500 bash tools/profile_round.sh $TAG > $OUT/profile_round.log 2>&1; stop_if_killed $?
   timeout -k 10 300 bash tools/gpu_trace_levels.sh > $OUT/levels.txt 2>&1; stop_if_killed $?
   timeout -k 10 200 python3 tools/gpu_stamps.py > $OUT/stamps.txt 2>&1; stop_if_killed $?
@@ -23,10 +23,10 @@ PY
   cat $OUT/levels.txt $OUT/stamps.txt
 else
   timeout -k 10 700 bash tools/profile_counters.sh $TAG > $OUT/counters.log 2>&1; stop_if_killed $?
-  timeout -k 10 400 python3 bench.py --config 5 --repeats 7 > $OUT/bench_config5.json 2> $OUT/bench_config5.err; stop_if_killed $?
-  timeout -k 10 300 python3 bench.py --config 2 --repeats 7 > $OUT/bench_config2.json 2> $OUT/bench_config2.err; stop_if_killed $?
-  timeout -k 10 300 python3 bench.py --members-per-gpu 8 --steps 20 --repeats 7 --cpu-workers 16 > $OUT/bench_members8.json 2>/dev/null; stop_if_killed $?
-  timeout -k 10 300 python3 bench.py --scheme RODASPR --steps 20 --repeats 7 --no-cpu-baseline > $OUT/bench_rodaspr.json 2>/dev/null; stop_if_killed $?
+  timeout -k 10 400 python3 bench.py --full --config 5 --repeats 7 > $OUT/bench_config5.json 2> $OUT/bench_config5.err; stop_if_killed $?
+  timeout -k 10 300 python3 bench.py --full --config 2 --repeats 7 > $OUT/bench_config2.json 2> $OUT/bench_config2.err; stop_if_killed $?
+  timeout -k 10 300 python3 bench.py --full --members-per-gpu 8 --steps 20 --repeats 7 --cpu-workers 16 > $OUT/bench_members8.json 2>/dev/null; stop_if_killed $?
+  timeout -k 10 300 python3 bench.py --full --scheme RODASPR --steps 20 --repeats 7 --no-cpu-baseline > $OUT/bench_rodaspr.json 2>/dev/null; stop_if_killed $?
   timeout -k 10 300 python3 tools/gpu_default_path_rate.py > $OUT/step_doubling_trial.txt 2>&1; stop_if_killed $?
   cat $OUT/step_doubling_trial.txt
   python3 - <<PY

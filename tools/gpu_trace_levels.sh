@@ -7,7 +7,7 @@ TAG=${1:-trace_levels}; shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/$TAG
 rm -rf $OUT && mkdir -p $OUT
-python3 /opt/rocm/bin/rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline "$@" > $OUT/bench.log 2>&1
+python3 "$(command -v rocprofv3)" --kernel-trace --output-format csv -d $OUT/trace -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline "$@" > $OUT/bench.log 2>&1
 python3 - <<PY | tee $OUT/levels.txt
 import csv, glob, collections
 agg = collections.defaultdict(list)

@@ -240,6 +240,31 @@ int tf_debug_stamps(tf_solver*, uint64_t* out, int32_t max_levels);
 int tf_kernel_count(void);
 const char* tf_kernel_name(int32_t kernel);
 
+/* ---- device probes: per-step reductions of model expressions on a resident state slot ----------
+ * code_object: the model's code object rebuilt with the generated probe block
+ * (codegen.lower_probes; built with the solver's parameter layout and sweep segment), of which
+ * only tfk_probe_partial / tfk_probe_final are launched.  kinds[nprobe]: 0 sum, 1 mean, 2 integral
+ * (np.trapz; periodic: dx * sum), 3 max, 4 min, 5 argmax, 6 argmin (x of the first extremal node);
+ * NaN as numpy has it.  nconst: host constants of the probe expressions (codegen spec
+ * "host_consts"), set per system by tf_probe_set_consts.  A record is queued on the solver's
+ * stream (no host wait) and writes one row [nsys][nprobe] into a device ring of `capacity` rows;
+ * a record that finds the ring full first copies it to host memory (one wait per `capacity`
+ * records).  A probe belongs to its solver: destroy it first. */
+typedef struct tf_probe tf_probe;
+int tf_probe_create(tf_solver*, const void* code_object, size_t code_size, int32_t nprobe,
+                    const int32_t* kinds, int32_t nconst, int32_t capacity, tf_probe** out);
+void tf_probe_destroy(tf_probe* probe);
+int tf_probe_set_consts(tf_probe*, const double* values /*[nsys][nconst]*/, int32_t nconst);
+/* coordinates of the nodes (argmax / argmin, probes that read x); ignored when the solver's model reads
+ * x itself: the probes then read the solver's plane (tf_set_x) */
+int tf_probe_set_x(tf_probe*, const double* x /*[nsys][N]*/);
+int tf_probe_record(tf_probe*, int32_t slot);
+/* waits, then hands over the oldest rows recorded since the last fetch (at most max_rows of them,
+ * out[row][nsys][nprobe]); *rows = how many */
+int tf_probe_fetch(tf_probe*, double* out, int64_t max_rows, int64_t* rows);
+/* rows recorded and not fetched yet (no wait) */
+int tf_probe_pending(tf_probe*, int64_t* rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,14 @@ SIGNATURES = {
     "tf_solver_kernel_block": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "tf_kernel_count": (C.c_int, []),
     "tf_kernel_name": (C.c_char_p, [C.c_int32]),
+    "tf_probe_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, c_int32_p, C.c_int32,
+                                  C.c_int32, C.POINTER(C.c_void_p)]),
+    "tf_probe_destroy": (None, [C.c_void_p]),
+    "tf_probe_set_consts": (C.c_int, [C.c_void_p, c_double_p, C.c_int32]),
+    "tf_probe_set_x": (C.c_int, [C.c_void_p, c_double_p]),
+    "tf_probe_record": (C.c_int, [C.c_void_p, C.c_int32]),
+    "tf_probe_fetch": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, c_int64_p]),
+    "tf_probe_pending": (C.c_int, [C.c_void_p, c_int64_p]),
 }
 
 
@@ -486,3 +494,62 @@ class DeviceSolver:
             if n.value:
                 out[name] = (ms.value, n.value)
         return out
+
+
+class DeviceProbe:
+    """``tf_probe``: the probe kernels of one probe set bound to one solver, and their ring."""
+
+    def __init__(self, solver, code, kinds, nconst, capacity=1024):
+        self.solver, self.lib = solver, solver.lib
+        self.nprobe, self.nconst, self.capacity = len(kinds), int(nconst), int(capacity)
+        self._code = C.create_string_buffer(code, len(code))
+        k = np.ascontiguousarray(kinds, dtype=np.int32)
+        handle = C.c_void_p()
+        self.lib.call("tf_probe_create", solver.handle, C.cast(self._code, C.c_void_p), len(code),
+                      self.nprobe, k.ctypes.data_as(c_int32_p), self.nconst, self.capacity, C.byref(handle))
+        self.handle = handle
+
+    def close(self):
+        if self.handle:
+            self.lib.dll.tf_probe_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check_open(self):
+        # (the tf_probe reads its solver's layout, stream and planes: not after the solver is gone)
+        if not self.solver.handle:
+            raise RuntimeError("the solver of this probe set was closed (rows not fetched before are lost)")
+
+    def set_consts(self, values):
+        """``values``: [nsys][nconst] host constants of the probe expressions."""
+        self._check_open()
+        v = _f64(values).reshape(self.solver.nsys, self.nconst)
+        self.lib.call("tf_probe_set_consts", self.handle, _dptr(v) if v.size else None, self.nconst)
+
+    def set_x(self, x):
+        self._check_open()
+        a = _f64(np.broadcast_to(np.asarray(x, dtype=float), (self.solver.nsys, self.solver.N)))
+        self.lib.call("tf_probe_set_x", self.handle, _dptr(a))
+
+    def record(self, slot):
+        self._check_open()
+        self.lib.call("tf_probe_record", self.handle, int(slot))
+
+    def pending(self):
+        self._check_open()
+        n = C.c_int64(0)
+        self.lib.call("tf_probe_pending", self.handle, C.byref(n))
+        return n.value
+
+    def fetch(self):
+        """Every row recorded since the last fetch, ``[rows][nsys][nprobe]`` (waits for the stream)."""
+        n = self.pending()
+        out = np.empty((n, self.solver.nsys, self.nprobe))
+        got = C.c_int64(0)
+        self.lib.call("tf_probe_fetch", self.handle, _dptr(out), n, C.byref(got))
+        return out[:got.value]

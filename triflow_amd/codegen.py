@@ -203,6 +203,25 @@ def _c_ident(name):
     return "v_" + "".join(ch if ch.isalnum() else "_" for ch in name)
 
 
+def _stencil_names(fields, pars, mp, parvec_mask):
+    """python identifier (as printed by SymPy) -> C identifier, the declarations that read them from the
+    register window / parameter array, and the names that are the same at every node."""
+    names = {}
+    decls = []
+    for f, name in enumerate(fields):
+        for off in range(-mp, mp + 1):
+            key = name if off == 0 else "%s_%s%d" % (name, "m" if off < 0 else "p", abs(off))
+            names[key] = _c_ident(key)
+            decls.append("const double %s = w[%d][%d];" % (_c_ident(key), f, off + mp))
+    for k, name in enumerate(pars):
+        names[name] = _c_ident(name)
+        decls.append("const double %s = par[%d];" % (_c_ident(name), k))
+    names["dx"] = "dx"
+    names["x"] = "xc"
+    uniform = {"dx"} | {name for k, name in enumerate(pars) if not (parvec_mask >> k) & 1}
+    return names, decls, uniform
+
+
 def lower_model(model, parvec_mask=0, seg=8, sweep_block=64):
     """Returns ``(source, spec)``: the per-model translation unit (without the
     skeleton includes' contents) and the dict of constants the runtime needs."""
@@ -231,21 +250,7 @@ def lower_model(model, parvec_mask=0, seg=8, sweep_block=64):
     pat_var = [(k // nvar) % nvar for k in sparse]
     pat_off = [(k // nvar) // nvar - real_mp for k in sparse]
 
-    # python identifier (as printed by SymPy) -> C identifier
-    names = {}
-    decls = []
-    for f, name in enumerate(fields):
-        for off in range(-mp, mp + 1):
-            key = name if off == 0 else "%s_%s%d" % (name, "m" if off < 0 else "p", abs(off))
-            names[key] = _c_ident(key)
-            decls.append("const double %s = w[%d][%d];" % (_c_ident(key), f, off + mp))
-    for k, name in enumerate(pars):
-        names[name] = _c_ident(name)
-        decls.append("const double %s = par[%d];" % (_c_ident(name), k))
-    names["dx"] = "dx"
-    names["x"] = "xc"
-
-    uniform = {"dx"} | {name for k, name in enumerate(pars) if not (parvec_mask >> k) & 1}
+    names, decls, uniform = _stencil_names(fields, pars, mp, parvec_mask)
     f_nodes = _printed_expressions(model._symbolic_args, model.F_array.tolist())
     j_nodes = _printed_expressions(model._symbolic_args, model._J_sparse_array.tolist())
     host_consts = {}
@@ -261,7 +266,8 @@ def lower_model(model, parvec_mask=0, seg=8, sweep_block=64):
 
     emit_f, f_c = emit_all(f_nodes)
     emit_j, j_c = emit_all(j_nodes)
-    uses_x = any("xc" in _tokens(s) for s in f_c + j_c)
+    # (x may also sit only in a hoisted divisor: tf_denK = xc)
+    uses_x = any("xc" in _tokens(s) for s in f_c + j_c + list(emit_f.denominators) + list(emit_j.denominators))
 
     # Jacobian entries that are the same at every node of a system (constant coefficients:
     # only dx, scalar parameters and constants): the solver kernels evaluate them once per
@@ -327,6 +333,55 @@ def lower_model(model, parvec_mask=0, seg=8, sweep_block=64):
                 j_alias=j_alias, j_alias_scale=j_alias_scale,
                 fields=fields, pars=pars)
     return src, spec
+
+
+#: reductions of a device probe, in the order of the TF_PROBE_* kinds of csrc/tf_probe.h
+PROBE_REDUCTIONS = ("sum", "mean", "integral", "max", "min", "argmax", "argmin")
+
+
+def lower_probes(model, exprs, reductions, parvec_mask=0):
+    """Device probes -> ``(block, spec)``: the C block that follows the model's own translation unit
+    (``TF_NPROBE`` ... and ``tf_eval_probe``, read by csrc/tf_probe.h) and the constants the runtime
+    needs.  ``exprs`` are discretised SymPy expressions over the model's symbolic arguments
+    (``probes.discretise``); they are printed by the same lambdify call as F and emitted by the same
+    ``_CEmitter``, so the per-node values are the bits NumPy computes from the printed expressions.
+    Uniform powers / libm calls become host constants of the probes (``spec["host_consts"]``, the
+    probe's own argument buffer: the model's parameter slots are not touched)."""
+    fields = list(model._dep_vars) + list(model._help_funcs)
+    pars = list(model._pars)
+    mp = max((model._window_range - 1) // 2, 1)
+    kinds = [PROBE_REDUCTIONS.index(r) for r in reductions]
+    names, decls, uniform = _stencil_names(fields, pars, mp, parvec_mask)
+    nodes = _printed_expressions(model._symbolic_args, list(exprs))
+    first = _CEmitter(names, uniform)               # pass 1: count divisor reuse
+    for n in nodes:
+        first.visit(n)
+    emit = _CEmitter(names, uniform)
+    emit.shared = first.den_count
+    out = [emit.visit(n) for n in nodes]
+    hc_list = [src_ for src_, _ in sorted(emit.host_consts.items(), key=lambda kv: kv[1])]
+    uses_x = any("xc" in _tokens(c) for c in out + list(emit.denominators))
+    lines = ["    " + d for d in decls]
+    lines += ["    (void)dx; (void)xc; (void)par; (void)tf_hc;"]
+    for den, k in sorted(emit.denominators.items(), key=lambda kv: kv[1]):
+        lines += ["    const double tf_den%d = %s;" % (k, den),
+                  "    const double tf_rden%d = 1.0 / tf_den%d;" % (k, k)]
+    lines += ["    P[%d] = %s;" % (i, c) for i, c in enumerate(out)]
+    block = "\n".join([
+        "// device probes, generated by triflow_amd.codegen.lower_probes -- do not edit",
+        "// " + " ; ".join("%s: %s" % (r, e) for r, e in zip(reductions, exprs)),
+        "#define TF_NPROBE %d" % len(out),
+        "#define TF_NPROBE_HC %d" % len(hc_list),
+        "#define TF_PROBE_USES_X %d" % (1 if uses_x else 0),
+        "static constexpr int tf_probe_kind[%d] = {%s};" % (max(len(kinds), 1),
+                                                           ", ".join(map(str, kinds)) or "0"),
+        "TF_DEVICE void tf_eval_probe(const double (&w)[TF_NVAR + TF_NH][2 * TF_MP + 1], "
+        "const double* par, const double* tf_hc, double dx, double xc, double* P) {",
+        "\n".join(lines),
+        "}",
+        ""])
+    spec = dict(nprobe=len(out), kinds=kinds, host_consts=hc_list, pars=pars, uses_x=int(uses_x))
+    return block, spec
 
 
 def _proportional_entries(model, j_uniform):

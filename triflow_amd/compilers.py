@@ -50,8 +50,8 @@ HIPCC_FLAGS = [*os.environ.get("TRIFLOW_HIPCC_OPT", "-O3").split(), "-std=c++17"
 
 #: translation units of the host runtime (see the header of csrc/tf_solver.h)
 RUNTIME_SOURCES = ("tf_rt_plan.cpp", "tf_rt_io.cpp", "tf_rt_steps.cpp", "tf_rt_diag.cpp",
-                   "tf_solver_sweeps.cpp", "tf_solver_linear.cpp")
-_SKELETON = ("tf_args.h", "tf_math.h", "tf_kernels.h", "tf_crs.h", "tf_coop_hip.h", "tf_cr2_hip.h", "tf_cr3_hip.h", "tf_entry_hip.h")
+                   "tf_solver_sweeps.cpp", "tf_solver_linear.cpp", "tf_rt_probe.cpp")
+_SKELETON = ("tf_args.h", "tf_math.h", "tf_kernels.h", "tf_crs.h", "tf_coop_hip.h", "tf_cr2_hip.h", "tf_cr3_hip.h", "tf_probe.h", "tf_entry_hip.h")
 _TU_HEAD = ('#include <hip/hip_runtime.h>\n'
             '#define TF_DEVICE __device__ __forceinline__\n'
             '%s'
@@ -118,8 +118,11 @@ def resource_usage(hsaco_path):
         return json.load(f)["kernels"]
 
 
-def _compile_code_object(model, source, tag, hsaco):
-    """hipcc on the generated translation unit -> ``hsaco`` (+ source and resource table next to it)."""
+def _compile_code_object(model, source, tag, hsaco, probes=False):
+    """hipcc on the generated translation unit -> ``hsaco`` (+ source and resource table next to it).
+    ``probes``: the unit carries a probe block (build_probe_code_object); only the probe kernels of that
+    object are ever launched, so there is no second build for the spill gate -- a probe kernel that
+    spills is refused instead."""
     global BUILD_COUNT
     BUILD_COUNT += 1
     hip = os.path.join(CACHE_DIR, "model_%s.hip" % tag)
@@ -144,6 +147,14 @@ def _compile_code_object(model, source, tag, hsaco):
     flags = list(HIPCC_FLAGS)
     usage = compile_with(flags, tmp)
     spilled = sorted(k for k, u in usage.items() if u.get("ScratchSize", 0) > 0)
+    if probes:
+        spilled_probe = [k for k in spilled if k.startswith("tfk_probe_")]
+        if spilled_probe:
+            os.remove(tmp)
+            raise codegen.UnsupportedExpression(
+                "the probe kernels (%s) need more registers than a wavefront has: "
+                "use fewer or simpler probes" % ", ".join(spilled_probe))
+        spilled = []
     alt_flags, alt_usage = None, None
     alt = hsaco[:-len(".hsaco")] + ".alt.hsaco"
     if spilled and "-O1" not in flags and "-O0" not in flags \
@@ -200,6 +211,39 @@ def alternate_of(hsaco_path):
     return (alt, kernels) if kernels and os.path.exists(alt) else (None, [])
 
 
+def _build_locked(model, source, tag, hsaco, probes=False):
+    """Compile ``source`` into ``hsaco`` unless it is in the cache already."""
+    if os.path.exists(hsaco):
+        return
+    # The ranks of one node may ask for the same uncached model at the same time (8 ranks of a
+    # sweep on a cold cache): one of them compiles, the others wait on the lock and find the
+    # code object.  Every file of the cache still appears by rename, never half written, so a
+    # file system without working locks costs duplicate compilations, not a torn file.
+    lock_path = hsaco + ".lock"
+    try:
+        with open(lock_path, "w") as lock:
+            try:
+                fcntl.flock(lock, fcntl.LOCK_EX)
+            except OSError:
+                pass
+            try:
+                if not os.path.exists(hsaco):
+                    _compile_code_object(model, source, tag, hsaco, probes)
+            finally:
+                try:
+                    fcntl.flock(lock, fcntl.LOCK_UN)
+                except OSError:
+                    pass
+    finally:
+        # (also after a failed or interrupted build: nothing of it stays in the cache)
+        for leftover in [lock_path] + [os.path.join(CACHE_DIR, n) for n in os.listdir(CACHE_DIR)
+                                        if n.endswith(".%d.tmp" % os.getpid())]:
+            try:
+                os.remove(leftover)
+            except OSError:
+                pass
+
+
 def build_code_object(model, parvec_mask=0, seg=None, sweep_block=None):
     """Model -> (path of the cached gfx950 code object, spec dict)."""
     seg = seg or int(os.environ.get("TRIFLOW_SWEEP_SEG", "8"))
@@ -210,35 +254,21 @@ def build_code_object(model, parvec_mask=0, seg=None, sweep_block=None):
     tag = codegen.source_hash(source, _skeleton_stamp(), " ".join(HIPCC_FLAGS), hipcc_version(), os.environ.get("TRIFLOW_SPILL_GATE", "kernel"), "elf")
     os.makedirs(CACHE_DIR, exist_ok=True)
     hsaco = os.path.join(CACHE_DIR, "model_%s.hsaco" % tag)
-    if not os.path.exists(hsaco):
-        # The ranks of one node may ask for the same uncached model at the same time (8 ranks of a
-        # sweep on a cold cache): one of them compiles, the others wait on the lock and find the
-        # code object.  Every file of the cache still appears by rename, never half written, so a
-        # file system without working locks costs duplicate compilations, not a torn file.
-        lock_path = hsaco + ".lock"
-        try:
-            with open(lock_path, "w") as lock:
-                try:
-                    fcntl.flock(lock, fcntl.LOCK_EX)
-                except OSError:
-                    pass
-                try:
-                    if not os.path.exists(hsaco):
-                        _compile_code_object(model, source, tag, hsaco)
-                finally:
-                    try:
-                        fcntl.flock(lock, fcntl.LOCK_UN)
-                    except OSError:
-                        pass
-        finally:
-            # (also after a failed or interrupted build: nothing of it stays in the cache)
-            for leftover in [lock_path] + [os.path.join(CACHE_DIR, n) for n in os.listdir(CACHE_DIR)
-                                            if n.endswith(".%d.tmp" % os.getpid())]:
-                try:
-                    os.remove(leftover)
-                except OSError:
-                    pass
+    _build_locked(model, source, tag, hsaco)
     return hsaco, spec
+
+
+def build_probe_code_object(model, probe_block, parvec_mask=0, seg=8, sweep_block=256):
+    """The model's translation unit followed by a probe block (codegen.lower_probes) -> path of the
+    cached code object.  Same parameter layout and sweep segment as the solver's own code object:
+    the probe kernels read that solver's planes and parameter slots."""
+    body, _ = codegen.lower_model(model, parvec_mask=parvec_mask, seg=seg, sweep_block=sweep_block)
+    source = _TU_HEAD % "" + body + probe_block + _TU_TAIL
+    tag = codegen.source_hash(source, _skeleton_stamp(), " ".join(HIPCC_FLAGS), hipcc_version(), "probe", "elf")
+    os.makedirs(CACHE_DIR, exist_ok=True)
+    hsaco = os.path.join(CACHE_DIR, "model_%s.hsaco" % tag)
+    _build_locked(model, source, tag, hsaco, probes=True)
+    return hsaco
 
 
 _hipcc_version = None

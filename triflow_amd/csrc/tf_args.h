@@ -326,8 +326,43 @@ struct TfTopArgs {                 // final 1-node system per ensemble member
 // ... and of a level that is ONE chunk per system (a 1 x 1 block's records fit the LDS twice as long)
 #define TF_CRS_TOPLEN(b) ((b) == 1 ? 512 : 256)
 
+// Device probes (tf_probe.h, tf_rt_probe.cpp): reductions of model expressions over the nodes of every
+// system, evaluated on a resident state slot.  tfk_probe_partial: grid (nsys * nblk, nseg), one thread per
+// segment of TF_PROBE_SEG nodes of a level-1 chunk, one partial per workgroup, probe and system;
+// tfk_probe_final: grid (nsys), reduces the partials of its system in a fixed order and writes one row of
+// the ring.  Reductions (codegen.PROBE_REDUCTIONS: same order):
+#define TF_PROBE_SUM 0
+#define TF_PROBE_MEAN 1
+#define TF_PROBE_INTEGRAL 2
+#define TF_PROBE_MAX 3
+#define TF_PROBE_MIN 4
+#define TF_PROBE_ARGMAX 5
+#define TF_PROBE_ARGMIN 6
+#define TF_PROBE_KINDS 7
+// nodes per thread of tfk_probe_partial: one thread per whole chunk left most of the GPU idle (config 3:
+// 31 250 chunks of 32 nodes, 14.8 us for 24 MB); segments of 8 as in the F sweep (TF_SEG)
+#define TF_PROBE_SEG 8
+struct TfProbeArgs {
+    TfLayout L;
+    const double* fields;          // [nvar] planes: the state slot probed
+    const double* helpers;         // [nh] planes
+    const double* parvec;          // [npar] planes (only those flagged vector are read)
+    const double* parsca;          // [npar][nsys] the solver's scalar parameters (+ the model's host constants)
+    const double* dx;              // [nsys]
+    const double* xcoord;          // 1 plane: x (the solver's when its model reads x, else the probe's own)
+    const double* hc;              // [nhc][nsys] host constants of the probe expressions
+    double* partial;               // [nsys][nprobe][nseg * nblk] (value, natural index) pairs
+    double* ends;                  // [nsys][nprobe][2]: f at natural nodes 0 and N-1 (integral)
+    int nblk;                      // workgroups of tfk_probe_partial per system and segment row
+    int nseg;                      // segments of TF_PROBE_SEG nodes per chunk
+    int capacity;                  // rows of the ring
+    int* cursor;                   // [0]: next row of the ring, [1]: systems done with the current row
+    double* ring;                  // [capacity][nsys][nprobe]
+};
+
 // Kernel table: index = launch id used by the runtime, name = entry point in
-// the per-model code object (tf_entry_hip.h).
+// the per-model code object (tf_entry_hip.h).  New entries go at the end: the
+// launch ids and the timing-mask bits of the others stay put.
 enum TfKernel {
     TFK_SWEEP_F = 0, TFK_SWEEP_FJ, TFK_SPMV, TFK_VEC, TFK_VEC_MAXABS, TFK_PERM, TFK_DIRICHLET,
     TFK_L1_FACTOR, TFK_L1_SOLVE, TFK_L1_ASM_MAT, TFK_L1_ASM_RHS, TFK_L1_BACKSUB,
@@ -335,7 +370,8 @@ enum TfKernel {
     TFK_TOP_FACTOR, TFK_TOP_SOLVE, TFK_BERR, TFK_DIFFNORM, TFK_L1_FACTOR_RHS, TFK_SWEEP_F_STAGE,
     TFK_CR_FACTOR, TFK_CR_FWD, TFK_CR_BWD, TFK_POKE, TFK_SWEEP_FJ_THETA, TFK_SWEEP_FJ_BDF2, TFK_GATHER,
     TFK_SWEEP_F_STAGE_RHS, TFK_L1_FWD2, TFK_L1_BACKSUB_U, TFK_CR_TAIL, TFK_L1_FWD2_BACKSUB, TFK_TINY_FACTOR, TFK_TINY_SOLVE,
-    TFK_S_FWD, TFK_S_BWD, TFK_SWEEP_F_STAGE_RHS_N, TFK_L1_SOLVE_CR, TFK_L1_FWD2_BACKSUB_CR, TFK_SWEEP_F_STAGE_RHS_MON, TFK_COUNT
+    TFK_S_FWD, TFK_S_BWD, TFK_SWEEP_F_STAGE_RHS_N, TFK_L1_SOLVE_CR, TFK_L1_FWD2_BACKSUB_CR, TFK_SWEEP_F_STAGE_RHS_MON,
+    TFK_PROBE_PARTIAL, TFK_PROBE_FINAL, TFK_COUNT
 };
 #define TF_KERNEL_NAMES { \
     "tfk_sweep_f", "tfk_sweep_fj", "tfk_spmv", "tfk_vec", "tfk_vec_maxabs", "tfk_perm", "tfk_dirichlet", \
@@ -345,4 +381,5 @@ enum TfKernel {
     "tfk_cr_factor", "tfk_cr_fwd", "tfk_cr_bwd", "tfk_poke", "tfk_sweep_fj_theta", "tfk_sweep_fj_bdf2", \
     "tfk_gather", "tfk_sweep_f_stage_rhs", "tfk_l1_fwd2", "tfk_l1_backsub_u", "tfk_cr_tail", \
     "tfk_l1_fwd2_backsub", "tfk_tiny_factor", "tfk_tiny_solve", "tfk_s_fwd", "tfk_s_bwd", "tfk_sweep_f_stage_rhs_n", \
-    "tfk_l1_solve_cr", "tfk_l1_fwd2_backsub_cr", "tfk_sweep_f_stage_rhs_mon" }
+    "tfk_l1_solve_cr", "tfk_l1_fwd2_backsub_cr", "tfk_sweep_f_stage_rhs_mon", \
+    "tfk_probe_partial", "tfk_probe_final" }

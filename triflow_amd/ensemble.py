@@ -13,7 +13,10 @@ table from rank 0 (``broadcast_table``).
 
 import numpy as np
 
+from .probes import ProbeSet
 from .tableaux import TABLEAUX
+
+__all__ = ["Ensemble", "shard_members", "broadcast_table"]
 
 
 def shard_members(n_members, rank, world_size):
@@ -98,6 +101,11 @@ class Ensemble:
         # started from -- the step reads it there and the history is never copied (tf_step_bdf2_from)
         self._nrot = s.nstate if self._keep is None else self._keep
         self._bdf_prev, self._bdf_dt = -1, None
+        # device probes: coordinates and per-member parameter values their host constants need
+        self._x = x
+        self._member_pars = [[np.asarray(v)[e] if np.ndim(v) >= 1 and np.shape(v)[0] == self.nsys else v
+                              for v in values] for e in range(self.nsys)]
+        self._probes, self._nsteps = None, 0
 
     def step(self, dt):
         """One fixed step of every member (asynchronous: returns after the launches)."""
@@ -116,6 +124,35 @@ class Ensemble:
                        hook_after=True, want_err=False)
         self.cur = dst
         self.t += dt
+        self._nsteps += 1
+        if self._probes is not None:
+            self._record_probes()
+
+    # ---- device probes (probes.py) ----------------------------------------------------
+    def add_probe(self, name, expression, reduce="sum"):
+        """Record ``reduce`` of ``expression`` over the nodes of every member, now and after every
+        ``step``; ``probes[name] = (t, values[rows, nsys])``.  Values of this rank's members only."""
+        if self._probes is None:
+            self._probes = ProbeSet(self.model)
+        self._probes.add(name, expression, reduce)
+        try:
+            self._record_probes()
+        except Exception:
+            # (no code object / no tf_probe for the new set: the probe is not kept, the others go on)
+            self._probes.remove(name)
+            raise
+
+    def remove_probe(self, name):
+        if self._probes is None:
+            raise KeyError(name)
+        self._probes.remove(name)
+
+    @property
+    def probes(self):
+        return self._probes.series() if self._probes is not None else {}
+
+    def _record_probes(self):
+        self._probes.record(self.solver, self.cur, self.t, self._nsteps, self._x, self._member_pars)
 
     def restart(self):
         """Back to the initial state and t = 0 (parameters, hook and factorisation plan stay; a
@@ -137,6 +174,8 @@ class Ensemble:
     check = sync
 
     def close(self):
+        if self._probes is not None:
+            self._probes.close()
         self.solver.close()
 
     def state(self):

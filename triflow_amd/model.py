@@ -141,6 +141,17 @@ class Model:
     def _parse(self):
         """strings -> SymPy (reference model.py:25-74, 480-542)."""
         x = sp.Symbol("x")
+        self._symb_indep_vars = (x,)
+        self._symb_dep_vars = tuple(sp.Function(n)(x) for n in self._dep_vars)
+        self._symb_help_funcs = tuple(sp.Function(n)(x) for n in self._help_funcs)
+        self._symb_pars = sp.symbols(self._pars)
+        self._symb_diff_eqs = self._parse_strings(self._diff_eqs)
+        self._symb_bdcs = self._parse_strings(self._bdcs)
+
+    def _parse_strings(self, equations):
+        """Strings of the model's language -> SymPy, in the model's namespace (also the
+        expressions of the device probes, probes.py)."""
+        x = self._symb_indep_vars[0]
         fields = self._dep_vars + self._help_funcs
         namespace = {"x": x}
         for order in range(1, _MAX_NAMESPACE_ORDER + 1):
@@ -149,25 +160,15 @@ class Model:
             for name in fields:
                 namespace["d%s%s" % ("x" * order, name)] = sp.Derivative(
                     sp.Function(name)(x), x, order)
-
-        self._symb_indep_vars = (x,)
-        self._symb_dep_vars = tuple(sp.Function(n)(x) for n in self._dep_vars)
-        self._symb_help_funcs = tuple(sp.Function(n)(x) for n in self._help_funcs)
-        self._symb_pars = sp.symbols(self._pars)
         # only the dependent variables are promoted to functions of x before
         # ``doit`` (the reference zips dep-var symbols only, model.py:515-521)
         promote = dict(zip(map(sp.Symbol, self._dep_vars),
                            self._symb_dep_vars + self._symb_help_funcs))
-
-        def parse(equations):
-            try:
-                return tuple(sp.sympify(eq, locals=namespace).xreplace(promote).doit()
-                             for eq in equations)
-            except (TypeError, sp.SympifyError):
-                raise ValueError("badly formated differential equations")
-
-        self._symb_diff_eqs = parse(self._diff_eqs)
-        self._symb_bdcs = parse(self._bdcs)
+        try:
+            return tuple(sp.sympify(eq, locals=namespace).xreplace(promote).doit()
+                         for eq in equations)
+        except (TypeError, sp.SympifyError):
+            raise ValueError("badly formated differential equations")
 
     # ----------------------------------------------------------- discretisation
     def _touch(self, name, offsets):

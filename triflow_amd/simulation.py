@@ -31,10 +31,14 @@ import warnings
 from collections import namedtuple
 from uuid import uuid1
 
+import numpy as np
 from numpy import isclose
 
 from . import schemes
-from .device import DirichletHook, null_hook
+from .device import DirichletHook, null_hook, stepper_for
+from .probes import ProbeSet
+
+__all__ = ["Simulation", "PostProcess", "Stream", "Timer"]
 
 log = logging.getLogger(__name__)
 log.addHandler(logging.NullHandler())
@@ -100,6 +104,7 @@ class Simulation:
         self._actual_timestamp = datetime.datetime.now()
         self._hook = hook
         self._container = None
+        self._probes = None
         self._iterator = self.compute()
 
     def _compute_one_step(self, t, fields, pars):
@@ -130,6 +135,8 @@ class Simulation:
                 t, fields, pars = self._compute_one_step(t, fields, pars)
                 self.i += 1
                 self.t, self.fields, self.parameters = t, fields, pars
+                if self._probes is not None:
+                    self._record_probes()
                 for pprocess in self.post_processes:
                     pprocess.function(self)
                 self.stream.emit(self)
@@ -220,6 +227,41 @@ class Simulation:
 
     def remove_post_process(self, name):
         self._pprocesses = [p for p in self._pprocesses if p.name != name]
+
+    # ---- device probes (probes.py) ----------------------------------------------------
+    def add_probe(self, name, expression, reduce="sum"):
+        """Record ``reduce`` of the model expression ``expression`` over the nodes after every step,
+        on the GPU (``probes.py``): the t0 row now, then one row where the post-processes run.  The
+        series is ``probes[name] = (t, values)``; the fields are never brought to the host for it."""
+        if self._probes is None:
+            self._probes = ProbeSet(self.model)
+        self._probes.add(name, expression, reduce)
+        try:
+            self._record_probes()
+        except Exception:
+            # (no code object / no tf_probe for the new set: the probe is not kept, the others go on)
+            self._probes.remove(name)
+            raise
+
+    def remove_probe(self, name):
+        if self._probes is None:
+            raise KeyError(name)
+        self._probes.remove(name)
+
+    @property
+    def probes(self):
+        """name -> (t, values): float64 arrays, one entry per recorded state."""
+        return self._probes.series(per_system=False) if self._probes is not None else {}
+
+    def _record_probes(self):
+        # the prologue of the device schemes (schemes._device_step): a state that is not resident is
+        # uploaded, one that is stays where it is
+        fields, pars = self.fields, self.parameters
+        stepper = stepper_for(self.model, fields, pars)
+        stepper.bind(fields, pars)
+        slot = stepper.acquire(fields)
+        self._probes.record(stepper.solver, slot, self.t, self.i, np.asarray(fields["x"]),
+                            [[pars[k] for k in stepper.compiled.pars]])
 
     def __iter__(self):
         return self.compute()

@@ -265,6 +265,31 @@ int tf_probe_fetch(tf_probe*, double* out, int64_t max_rows, int64_t* rows);
 /* rows recorded and not fetched yet (no wait) */
 int tf_probe_pending(tf_probe*, int64_t* rows);
 
+/* ---- device recorders: decimated space-time series of model expressions on a resident state slot ----
+ * code_object: the model's code object rebuilt with the generated record block (codegen.lower_records;
+ * built with the solver's parameter layout and sweep segment), of which only tfk_record is launched.
+ * geometry[nrec][6]: the expression of the block (recorders may share one), pool (0 sample, 1 max,
+ * 2 min, 3 mean), start, stop, step of the window of nodes (0 <= start < stop <= N, step >= 1) and
+ * the rows of the recorder's device ring (>= 2: two halves).
+ * Column j of a recorder is its expression pooled over nodes start + j*step ...
+ * min(start + (j+1)*step, stop) - 1; NaN as numpy has it; the mean's sum is added in a fixed order.
+ * A record is queued on the solver's stream (no host wait) and writes one row [nsys][ncols]; a half
+ * of the ring that is full is copied to page-locked host memory by a stream of the recorder's own
+ * while the records go on into the other half.  A recorder belongs to its solver: destroy it first. */
+typedef struct tf_record tf_record;
+int tf_record_create(tf_solver*, const void* code_object, size_t code_size, int32_t nrec,
+                     const int32_t* geometry, int32_t nconst, tf_record** out);
+void tf_record_destroy(tf_record* record);
+int tf_record_set_consts(tf_record*, const double* values /*[nsys][nconst]*/, int32_t nconst);
+/* coordinates of the nodes (expressions that read x); ignored when the solver's model reads x itself */
+int tf_record_set_x(tf_record*, const double* x /*[nsys][N]*/);
+int tf_record_record(tf_record*, int32_t which, int32_t slot);
+/* waits, then hands over the oldest rows of recorder `which` recorded since its last fetch (at most
+ * max_rows of them, out[row][nsys][ncols]); *rows = how many */
+int tf_record_fetch(tf_record*, int32_t which, double* out, int64_t max_rows, int64_t* rows);
+/* rows of recorder `which` recorded and not fetched yet (no wait) */
+int tf_record_pending(tf_record*, int32_t which, int64_t* rows);
+
 #ifdef __cplusplus
 }
 #endif

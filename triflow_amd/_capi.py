@@ -105,6 +105,14 @@ SIGNATURES = {
     "tf_probe_record": (C.c_int, [C.c_void_p, C.c_int32]),
     "tf_probe_fetch": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, c_int64_p]),
     "tf_probe_pending": (C.c_int, [C.c_void_p, c_int64_p]),
+    "tf_record_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, c_int32_p, C.c_int32,
+                                   C.POINTER(C.c_void_p)]),
+    "tf_record_destroy": (None, [C.c_void_p]),
+    "tf_record_set_consts": (C.c_int, [C.c_void_p, c_double_p, C.c_int32]),
+    "tf_record_set_x": (C.c_int, [C.c_void_p, c_double_p]),
+    "tf_record_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "tf_record_fetch": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int64, c_int64_p]),
+    "tf_record_pending": (C.c_int, [C.c_void_p, C.c_int32, c_int64_p]),
 }
 
 
@@ -552,4 +560,65 @@ class DeviceProbe:
         out = np.empty((n, self.solver.nsys, self.nprobe))
         got = C.c_int64(0)
         self.lib.call("tf_probe_fetch", self.handle, _dptr(out), n, C.byref(got))
+        return out[:got.value]
+
+
+class DeviceRecord:
+    """``tf_record``: the record kernel of one recorder set bound to one solver, and the rings."""
+
+    def __init__(self, solver, code, geometry, nconst):
+        """``geometry``: per recorder ``(expression, pool, start, stop, step, rows of the ring)``."""
+        self.solver, self.lib = solver, solver.lib
+        self.nconst = int(nconst)
+        g = np.ascontiguousarray(geometry, dtype=np.int32).reshape(-1, 6)
+        self.ncols = [-(-(int(r[3]) - int(r[2])) // int(r[4])) for r in g]
+        self._code = C.create_string_buffer(code, len(code))
+        handle = C.c_void_p()
+        self.lib.call("tf_record_create", solver.handle, C.cast(self._code, C.c_void_p), len(code),
+                      len(g), g.ctypes.data_as(c_int32_p), self.nconst, C.byref(handle))
+        self.handle = handle
+
+    def close(self):
+        if self.handle:
+            self.lib.dll.tf_record_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check_open(self):
+        # (the tf_record reads its solver's layout, stream and planes: not after the solver is gone)
+        if not self.solver.handle:
+            raise RuntimeError("the solver of this recorder set was closed (rows not fetched before are lost)")
+
+    def set_consts(self, values):
+        """``values``: [nsys][nconst] host constants of the record expressions."""
+        self._check_open()
+        v = _f64(values).reshape(self.solver.nsys, self.nconst)
+        self.lib.call("tf_record_set_consts", self.handle, _dptr(v) if v.size else None, self.nconst)
+
+    def set_x(self, x):
+        self._check_open()
+        a = _f64(np.broadcast_to(np.asarray(x, dtype=float), (self.solver.nsys, self.solver.N)))
+        self.lib.call("tf_record_set_x", self.handle, _dptr(a))
+
+    def record(self, which, slot):
+        self._check_open()
+        self.lib.call("tf_record_record", self.handle, int(which), int(slot))
+
+    def pending(self, which):
+        self._check_open()
+        n = C.c_int64(0)
+        self.lib.call("tf_record_pending", self.handle, int(which), C.byref(n))
+        return n.value
+
+    def fetch(self, which):
+        """Every row of recorder ``which`` recorded since its last fetch, ``[rows][nsys][ncols]``."""
+        n = self.pending(which)
+        out = np.empty((n, self.solver.nsys, self.ncols[which]))
+        got = C.c_int64(0)
+        self.lib.call("tf_record_fetch", self.handle, int(which), _dptr(out), n, C.byref(got))
         return out[:got.value]

@@ -339,18 +339,15 @@ def lower_model(model, parvec_mask=0, seg=8, sweep_block=64):
 PROBE_REDUCTIONS = ("sum", "mean", "integral", "max", "min", "argmax", "argmin")
 
 
-def lower_probes(model, exprs, reductions, parvec_mask=0):
-    """Device probes -> ``(block, spec)``: the C block that follows the model's own translation unit
-    (``TF_NPROBE`` ... and ``tf_eval_probe``, read by csrc/tf_probe.h) and the constants the runtime
-    needs.  ``exprs`` are discretised SymPy expressions over the model's symbolic arguments
-    (``probes.discretise``); they are printed by the same lambdify call as F and emitted by the same
-    ``_CEmitter``, so the per-node values are the bits NumPy computes from the printed expressions.
-    Uniform powers / libm calls become host constants of the probes (``spec["host_consts"]``, the
-    probe's own argument buffer: the model's parameter slots are not touched)."""
+def _lower_node_expressions(model, exprs, parvec_mask):
+    """What the probes and the recorders share: discretised SymPy expressions over the model's symbolic
+    arguments, printed by the same lambdify call as F and emitted by the same ``_CEmitter``.  Returns
+    the lines that open the per-node body (the window / parameter names, the hoisted divisors), the C
+    expressions, the uniform powers / libm calls evaluated on the host, whether ``x`` is read, and the
+    model's parameter names."""
     fields = list(model._dep_vars) + list(model._help_funcs)
     pars = list(model._pars)
     mp = max((model._window_range - 1) // 2, 1)
-    kinds = [PROBE_REDUCTIONS.index(r) for r in reductions]
     names, decls, uniform = _stencil_names(fields, pars, mp, parvec_mask)
     nodes = _printed_expressions(model._symbolic_args, list(exprs))
     first = _CEmitter(names, uniform)               # pass 1: count divisor reuse
@@ -366,6 +363,19 @@ def lower_probes(model, exprs, reductions, parvec_mask=0):
     for den, k in sorted(emit.denominators.items(), key=lambda kv: kv[1]):
         lines += ["    const double tf_den%d = %s;" % (k, den),
                   "    const double tf_rden%d = 1.0 / tf_den%d;" % (k, k)]
+    return lines, out, hc_list, uses_x, pars
+
+
+def lower_probes(model, exprs, reductions, parvec_mask=0):
+    """Device probes -> ``(block, spec)``: the C block that follows the model's own translation unit
+    (``TF_NPROBE`` ... and ``tf_eval_probe``, read by csrc/tf_probe.h) and the constants the runtime
+    needs.  ``exprs`` are discretised SymPy expressions over the model's symbolic arguments
+    (``probes.discretise``); they are printed by the same lambdify call as F and emitted by the same
+    ``_CEmitter``, so the per-node values are the bits NumPy computes from the printed expressions.
+    Uniform powers / libm calls become host constants of the probes (``spec["host_consts"]``, the
+    probe's own argument buffer: the model's parameter slots are not touched)."""
+    kinds = [PROBE_REDUCTIONS.index(r) for r in reductions]
+    lines, out, hc_list, uses_x, pars = _lower_node_expressions(model, exprs, parvec_mask)
     lines += ["    P[%d] = %s;" % (i, c) for i, c in enumerate(out)]
     block = "\n".join([
         "// device probes, generated by triflow_amd.codegen.lower_probes -- do not edit",
@@ -381,6 +391,35 @@ def lower_probes(model, exprs, reductions, parvec_mask=0):
         "}",
         ""])
     spec = dict(nprobe=len(out), kinds=kinds, host_consts=hc_list, pars=pars, uses_x=int(uses_x))
+    return block, spec
+
+
+#: pools of a device recorder, in the order of the TF_REC_* pools of csrc/tf_args.h
+RECORD_POOLS = ("sample", "max", "min", "mean")
+
+
+def lower_records(model, exprs, parvec_mask=0):
+    """Device recorders -> ``(block, spec)``: the C block that follows the model's own translation unit
+    (``TF_NREC`` ... and ``tf_eval_record``, read by csrc/tf_record.h; expression ``k`` is case ``k``)
+    and the constants the runtime needs.  Lowered as the probes are (``_lower_node_expressions``): the
+    per-node values are the bits NumPy computes from the printed expressions; the host constants go
+    into the recorders' own argument buffer (``spec["host_consts"]``)."""
+    lines, out, hc_list, uses_x, pars = _lower_node_expressions(model, exprs, parvec_mask)
+    lines += ["    switch (k) {"]
+    lines += ["    case %d: return %s;" % (i, c) for i, c in enumerate(out)]
+    lines += ["    default: return 0.0;", "    }"]
+    block = "\n".join([
+        "// device recorders, generated by triflow_amd.codegen.lower_records -- do not edit",
+        "// " + " ; ".join(str(e) for e in exprs),
+        "#define TF_NREC %d" % len(out),
+        "#define TF_NREC_HC %d" % len(hc_list),
+        "#define TF_REC_USES_X %d" % (1 if uses_x else 0),
+        "TF_DEVICE double tf_eval_record(int k, const double (&w)[TF_NVAR + TF_NH][2 * TF_MP + 1], "
+        "const double* par, const double* tf_hc, double dx, double xc) {",
+        "\n".join(lines),
+        "}",
+        ""])
+    spec = dict(nrec=len(out), host_consts=hc_list, pars=pars, uses_x=int(uses_x))
     return block, spec
 
 

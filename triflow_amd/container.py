@@ -240,6 +240,29 @@ def _plain(value):
     return str(value)
 
 
+def write_series(path, t, x, fields, metadata=None):
+    """A space-time series that did not come through a simulation's stream (a device recorder:
+    ``recorders.py``) as a container directory: ``metadata.yml`` and ``data.nc`` in the layout above,
+    which ``retrieve_container(path)`` reads.  ``t`` [nt], ``x`` [nx], ``fields``: {name: [nt, nx]}."""
+    path = os.path.abspath(path)
+    t, x = np.asarray(t, dtype=float), np.asarray(x, dtype=float)
+    if t.ndim != 1 or x.ndim != 1:
+        raise ValueError("write_series: t and x are one-dimensional")
+    data = {"t": t, "x": x}
+    for key, value in fields.items():
+        value = np.asarray(value, dtype=float)
+        if key in ("t", "x") or value.shape != (t.size, x.size):
+            raise ValueError("write_series: field %r of shape %r, (%d, %d) expected under a name of its own"
+                             % (key, value.shape, t.size, x.size))
+        data[str(key)] = value
+    attrs = {str(k): _plain(v) for k, v in dict(metadata or {}).items()}
+    os.makedirs(path, exist_ok=True)
+    with open(os.path.join(path, "metadata.yml"), "w") as f:
+        yaml.safe_dump(attrs, f, default_flow_style=False)
+    _write_nc(os.path.join(path, "data.nc"), data, attrs)
+    return path
+
+
 def retrieve_container(path, isel="all", lazy=False):
     """Reference ``triflow.retrieve_container`` (``triflow/__init__.py:9``)."""
     return TriflowContainer.retrieve(path, isel=isel)

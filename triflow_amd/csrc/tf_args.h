@@ -360,6 +360,37 @@ struct TfProbeArgs {
     double* ring;                  // [capacity][nsys][nprobe]
 };
 
+// Device recorders (tf_record.h, tf_rt_record.cpp): decimated space-time series of model expressions.
+// Column j of a recorder covers the bin of natural nodes start + j*step ... min(start + (j+1)*step, stop) - 1
+// of every system; tfk_record evaluates expression `which` of the record block on a resident state slot
+// and stores one row [nsys][ncols] of the recorder's ring.  Pools:
+#define TF_REC_SAMPLE 0            // the expression at the bin's first node
+#define TF_REC_MAX 1               // over the bin's nodes, NaN as numpy has it (tf_probe_combine)
+#define TF_REC_MIN 2
+#define TF_REC_MEAN 3              // sum in a fixed order / the bin's node count
+// threads of a workgroup of tfk_record; `split` of them share a bin (a power of two <= TF_REC_BLOCK)
+#define TF_REC_BLOCK 256
+struct TfRecordArgs {
+    TfLayout L;
+    const double* fields;          // [nvar] planes: the state slot recorded
+    const double* helpers;         // [nh] planes
+    const double* parvec;          // [npar] planes (only those flagged vector are read)
+    const double* parsca;          // [npar][nsys] the solver's scalar parameters (+ the model's host constants)
+    const double* dx;              // [nsys]
+    const double* xcoord;          // 1 plane: x (the solver's when its model reads x, else the recorder's own)
+    const double* hc;              // [nhc][nsys] host constants of the record expressions
+    int which;                     // expression of the record block (tf_eval_record's first argument)
+    int pool;                      // TF_REC_*
+    int start, stop, step;         // the window of nodes (slice.indices(N), step >= 1)
+    int ncols;                     // ceil((stop - start) / step)
+    int split;                     // threads per bin
+    int part;                      // nodes per thread = ceil(step / split)
+    int nblk;                      // workgroups per system
+    int capacity;                  // rows of the ring (both halves)
+    int* cursor;                   // [0]: next row of the ring (wraps at capacity), [1]: workgroups done with it
+    double* ring;                  // [capacity][nsys][ncols]
+};
+
 // Kernel table: index = launch id used by the runtime, name = entry point in
 // the per-model code object (tf_entry_hip.h).  New entries go at the end: the
 // launch ids and the timing-mask bits of the others stay put.
@@ -371,7 +402,8 @@ enum TfKernel {
     TFK_CR_FACTOR, TFK_CR_FWD, TFK_CR_BWD, TFK_POKE, TFK_SWEEP_FJ_THETA, TFK_SWEEP_FJ_BDF2, TFK_GATHER,
     TFK_SWEEP_F_STAGE_RHS, TFK_L1_FWD2, TFK_L1_BACKSUB_U, TFK_CR_TAIL, TFK_L1_FWD2_BACKSUB, TFK_TINY_FACTOR, TFK_TINY_SOLVE,
     TFK_S_FWD, TFK_S_BWD, TFK_SWEEP_F_STAGE_RHS_N, TFK_L1_SOLVE_CR, TFK_L1_FWD2_BACKSUB_CR, TFK_SWEEP_F_STAGE_RHS_MON,
-    TFK_PROBE_PARTIAL, TFK_PROBE_FINAL, TFK_COUNT
+    TFK_PROBE_PARTIAL, TFK_PROBE_FINAL,
+    TFK_RECORD, TFK_COUNT          // (from TFK_RECORD on: TF_KERNEL_NAMES_RECORD)
 };
 #define TF_KERNEL_NAMES { \
     "tfk_sweep_f", "tfk_sweep_fj", "tfk_spmv", "tfk_vec", "tfk_vec_maxabs", "tfk_perm", "tfk_dirichlet", \
@@ -383,3 +415,13 @@ enum TfKernel {
     "tfk_l1_fwd2_backsub", "tfk_tiny_factor", "tfk_tiny_solve", "tfk_s_fwd", "tfk_s_bwd", "tfk_sweep_f_stage_rhs_n", \
     "tfk_l1_solve_cr", "tfk_l1_fwd2_backsub_cr", "tfk_sweep_f_stage_rhs_mon", \
     "tfk_probe_partial", "tfk_probe_final" }
+// ... continued: the kernels of the recorders (ids TFK_RECORD ...), a table of their own
+#define TF_KERNEL_NAMES_RECORD { "tfk_record" }
+static inline const char* tf_kernel_entry(int kernel) {
+    static const char* const base[] = TF_KERNEL_NAMES;
+    static const char* const rec[] = TF_KERNEL_NAMES_RECORD;
+    static_assert(sizeof(base) / sizeof(base[0]) == TFK_RECORD, "TF_KERNEL_NAMES and TfKernel differ");
+    static_assert(sizeof(rec) / sizeof(rec[0]) == TFK_COUNT - TFK_RECORD, "TF_KERNEL_NAMES_RECORD and TfKernel differ");
+    if (kernel < 0 || kernel >= TFK_COUNT) return "";
+    return kernel < TFK_RECORD ? base[kernel] : rec[kernel - TFK_RECORD];
+}

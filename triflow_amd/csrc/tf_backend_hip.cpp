@@ -164,7 +164,6 @@ void d2d(void* dst, const void* src, size_t bytes, Stream* s) {
 }
 
 Module* module_load(const void* image, size_t) {
-    static const char* names[TFK_COUNT] = TF_KERNEL_NAMES;
     Module* m = new Module();
     hipError_t err = hipModuleLoadData(&m->mod, image);
     if (err != hipSuccess) {
@@ -172,11 +171,11 @@ Module* module_load(const void* image, size_t) {
         check(err, "hipModuleLoadData (is the code object built for this GPU, gfx950?)");
     }
     for (int k = 0; k < TFK_COUNT; ++k) {
-        err = hipModuleGetFunction(&m->fn[k], m->mod, names[k]);
+        err = hipModuleGetFunction(&m->fn[k], m->mod, tf_kernel_entry(k));
         if (err != hipSuccess) {
             (void)hipModuleUnload(m->mod);
             delete m;
-            throw std::runtime_error(std::string("kernel missing from code object: ") + names[k]);
+            throw std::runtime_error(std::string("kernel missing from code object: ") + tf_kernel_entry(k));
         }
     }
     // Debug aid for compiler bisection: TF_ALT_HSACO=<file> TF_ALT_MASK=<bits> takes
@@ -192,7 +191,7 @@ Module* module_load(const void* image, size_t) {
                 hipModule_t am;
                 if (hipModuleLoadData(&am, img.data()) == hipSuccess)
                     for (int k = 0; k < TFK_COUNT; ++k)
-                        if ((mask >> k) & 1ul) (void)hipModuleGetFunction(&m->fn[k], am, names[k]);
+                        if ((mask >> k) & 1ul) (void)hipModuleGetFunction(&m->fn[k], am, tf_kernel_entry(k));
             }
         }
         if (f) fclose(f);
@@ -200,14 +199,13 @@ Module* module_load(const void* image, size_t) {
     return m;
 }
 void module_add_alternate(Module* m, const void* image, size_t, uint64_t mask) {
-    static const char* names[TFK_COUNT] = TF_KERNEL_NAMES;
     if (!m || !mask) return;
     if (m->alt) throw std::runtime_error("module_add_alternate: one alternate build per model");
     check(hipModuleLoadData(&m->alt, image), "hipModuleLoadData (alternate build)");
     for (int k = 0; k < TFK_COUNT; ++k)
         if ((mask >> k) & 1ull) {
-            if (hipModuleGetFunction(&m->fn[k], m->alt, names[k]) != hipSuccess)
-                throw std::runtime_error(std::string("kernel missing from the alternate code object: ") + names[k]);
+            if (hipModuleGetFunction(&m->fn[k], m->alt, tf_kernel_entry(k)) != hipSuccess)
+                throw std::runtime_error(std::string("kernel missing from the alternate code object: ") + tf_kernel_entry(k));
         }
 }
 void module_unload(Module* m) {
@@ -309,5 +307,17 @@ float event_elapsed_ms(Event* a, Event* b) {
     TF_HIP(hipEventElapsedTime(&ms, a->e, b->e));
     return ms;
 }
+
+void* host_alloc(size_t bytes) {
+    void* p = nullptr;
+    TF_HIP(hipHostMalloc(&p, bytes ? bytes : 8, hipHostMallocDefault));
+    return p;
+}
+void host_free(void* p) { if (p) (void)hipHostFree(p); }
+void d2h_async(void* dst, const void* src, size_t bytes, Stream* s) {
+    TF_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s->s));
+}
+void stream_wait_event(Stream* s, Event* e) { TF_HIP(hipStreamWaitEvent(s->s, e->e, 0)); }
+void event_sync(Event* e) { TF_HIP(hipEventSynchronize(e->e)); }
 
 }  // namespace tfb

@@ -8,6 +8,7 @@
 #include "tf_cr2_hip.h"
 #include "tf_cr3_hip.h"
 #include "tf_probe.h"
+#include "tf_record.h"
 
 #define TF_GID ((int)(blockIdx.x * blockDim.x + threadIdx.x))
 

@@ -1,0 +1,130 @@
+// Device recorders: decimated space-time series of model expressions (h(x, t) of a film, a kymograph).
+//
+// A recorder is an expression in the model's string language, lowered by codegen.lower_records to one
+// case of tf_eval_record (same emitter as tf_eval_F and tf_eval_probe: the per-node values are the bits
+// the reference's lambdified NumPy code computes), a window of nodes start:stop:step and a pool over the
+// nodes of each bin (TF_REC_*, tf_args.h).  The generated record block defines TF_NREC, TF_NREC_HC,
+// TF_REC_USES_X and tf_eval_record before this header is read; every other code object compiles the
+// no-op defaults below (every code object holds every kernel of the table, tf_args.h).
+//
+// The walk and the combine are what the host harness of the test suite (tests/record_host/) also
+// compiles with g++; the kernel itself is at the end of the file.
+#pragma once
+
+#ifndef TF_NREC
+#define TF_NREC 0
+#define TF_NREC_HC 0
+#define TF_REC_USES_X 0
+TF_DEVICE double tf_eval_record(int, const double (&)[TF_NVAR + TF_NH][2 * TF_MP + 1], const double*,
+                                const double*, double, double) { return 0.0; }
+#endif
+
+// b after a.  Maxima / minima are the probes' operator (numpy's: NaN wins; the order of the operands
+// does not matter), the mean's sum is added in the order the caller fixes.
+TF_DEVICE double tf_rec_combine(int pool, double a, double b) {
+    if (pool == TF_REC_MEAN) return a + b;
+    return tf_probe_combine(pool == TF_REC_MAX ? TF_PROBE_MAX : TF_PROBE_MIN, TfProbeAcc{a, 0.0},
+                            TfProbeAcc{b, 0.0}).v;
+}
+
+// nodes of bin j ("sample": its first node only)
+TF_DEVICE int tf_rec_count(const TfRecordArgs& a, int j) {
+    if (a.pool == TF_REC_SAMPLE) return 1;
+    const int g0 = a.start + j * a.step;
+    return (a.stop - g0 < a.step ? a.stop : g0 + a.step) - g0;
+}
+
+// One thread: the natural nodes g0 ... g0 + n - 1 (n >= 1, inside the system) of system e, folded in node
+// order.  The register window slides along the nodes as in the F sweep and in tf_probe_walk (ghosts
+// through tf_nbr, wrapped or clamped at the ends of the system); a walk that leaves its chunk goes on
+// at row 0 of the next one with the window it holds.
+TF_DEVICE double tf_record_walk(const TfRecordArgs& a, int e, int g0, int n) {
+    const TfLayout& L = a.L;
+    int p, i;
+    tf_locate(L, g0, p, i);
+    int len = tf_len(L, p);
+    double par[TF_NPAR > 0 ? TF_NPAR : 1];
+#pragma unroll
+    for (int k = 0; k < TF_NPAR; ++k) par[k] = tf_par_is_vec[k] ? 0.0 : a.parsca[k * L.nsys + e];
+    double hc[TF_NREC_HC > 0 ? TF_NREC_HC : 1];
+#pragma unroll
+    for (int k = 0; k < TF_NREC_HC; ++k) hc[k] = a.hc[k * L.nsys + e];
+    const double dx = a.dx[e];
+    auto ld = [&](int f, int ii) -> double {
+        const int64_t s = (ii >= 0 && ii < len) ? tf_idx(L, e * L.P + p, ii) : tf_nbr(L, e, p, len, 0, ii);
+        return f >= TF_NVAR ? a.helpers[(int64_t)(f - TF_NVAR) * L.plane + s]
+                            : a.fields[(int64_t)f * L.plane + s];
+    };
+    double w[TF_NVAR + TF_NH][2 * TF_MP + 1];
+#pragma unroll
+    for (int f = 0; f < TF_NVAR + TF_NH; ++f)
+#pragma unroll
+        for (int o = 1; o < 2 * TF_MP + 1; ++o) w[f][o] = ld(f, i + o - 1 - TF_MP);
+    double acc = 0.0;
+    for (int j = 0; j < n; ++j) {
+#pragma unroll
+        for (int f = 0; f < TF_NVAR + TF_NH; ++f) {
+#pragma unroll
+            for (int o = 0; o < 2 * TF_MP; ++o) w[f][o] = w[f][o + 1];
+            w[f][2 * TF_MP] = ld(f, i + TF_MP);
+        }
+        const int64_t s = tf_idx(L, e * L.P + p, i);
+#pragma unroll
+        for (int k = 0; k < TF_NPAR; ++k)
+            if (tf_par_is_vec[k]) par[k] = a.parvec[(int64_t)k * L.plane + s];
+        const double xc = TF_REC_USES_X ? a.xcoord[s] : 0.0;
+        const double v = tf_eval_record(a.which, w, par, hc, dx, xc);
+        acc = j == 0 ? v : tf_rec_combine(a.pool, acc, v);
+        if (++i == len && p + 1 < L.P) { ++p; i = 0; len = tf_len(L, p); }
+    }
+    return acc;
+}
+
+// part s of bin j: nodes s * part ... of the bin (the caller checks that the part holds a node)
+TF_DEVICE double tf_record_part(const TfRecordArgs& a, int e, int j, int s) {
+    const int cnt = tf_rec_count(a, j), lo = s * a.part;
+    return tf_record_walk(a, e, a.start + j * a.step + lo, cnt - lo < a.part ? cnt - lo : a.part);
+}
+
+// the parts of bin j, in their order, to the value of column j
+TF_DEVICE double tf_record_finish(const TfRecordArgs& a, int j, const double* parts) {
+    const int cnt = tf_rec_count(a, j);
+    double acc = parts[0];
+    for (int s = 1; s * a.part < cnt; ++s) acc = tf_rec_combine(a.pool, acc, parts[s]);
+    return a.pool == TF_REC_MEAN ? acc / (double)cnt : acc;
+}
+
+#if defined(__HIPCC__)
+// grid (nsys * nblk), TF_REC_BLOCK threads: `split` neighbouring threads share a bin, thread s of them
+// walks `part` nodes of it (at most 8 where the bin allows: the threads of a wavefront then read a few
+// whole rows of neighbouring chunks, and a bin of 64 nodes keeps 8 threads busy instead of one); the
+// parts meet in LDS and the first TF_REC_BLOCK / split threads combine them in part order and store the
+// columns of the workgroup side by side in row cursor[0] of the ring.  The row cursor lives in device
+// memory, as the probes' does: the last workgroup to be done with the row (an integer counter) moves it
+// on, wrapping at the ring's capacity -- a replayed launch writes the next row.  No floating-point atomics.
+extern "C" __global__ void __launch_bounds__(TF_REC_BLOCK) tfk_record(TfRecordArgs a) {
+    if constexpr (TF_NREC > 0) {
+        __shared__ double parts[TF_REC_BLOCK];
+        const int e = blockIdx.x / a.nblk, blk = blockIdx.x - e * a.nblk;
+        const int cpb = TF_REC_BLOCK / a.split;
+        const int row = *(volatile int*)&a.cursor[0];
+        const int c = threadIdx.x / a.split, s = threadIdx.x - c * a.split;
+        const int j = blk * cpb + c;
+        double v = 0.0;
+        if (j < a.ncols && s * a.part < tf_rec_count(a, j)) v = tf_record_part(a, e, j, s);
+        parts[threadIdx.x] = v;
+        __syncthreads();
+        const int jj = blk * cpb + threadIdx.x;
+        if (threadIdx.x < cpb && jj < a.ncols && row >= 0 && row < a.capacity)
+            a.ring[((int64_t)row * a.L.nsys + e) * a.ncols + jj] = tf_record_finish(a, jj, parts + threadIdx.x * a.split);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            __threadfence();
+            if (atomicAdd(&a.cursor[1], 1) == (int)gridDim.x - 1) {
+                atomicExch(&a.cursor[1], 0);
+                atomicExch(&a.cursor[0], row + 1 < a.capacity ? row + 1 : 0);
+            }
+        }
+    }
+}
+#endif

@@ -33,8 +33,7 @@ int tf_set_device(int32_t ordinal) {
 
 int tf_kernel_count(void) { return TFK_COUNT; }
 const char* tf_kernel_name(int32_t kernel) {
-    static const char* names[TFK_COUNT] = TF_KERNEL_NAMES;
-    return (kernel >= 0 && kernel < TFK_COUNT) ? names[kernel] : "";
+    return tf_kernel_entry(kernel);
 }
 
 int tf_model_create(const tf_model_spec* spec, const void* code, size_t size, tf_model** out) {

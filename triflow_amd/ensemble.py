@@ -14,6 +14,7 @@ table from rank 0 (``broadcast_table``).
 import numpy as np
 
 from .probes import ProbeSet
+from .recorders import RecorderSet
 from .tableaux import TABLEAUX
 
 __all__ = ["Ensemble", "shard_members", "broadcast_table"]
@@ -105,7 +106,7 @@ class Ensemble:
         self._x = x
         self._member_pars = [[np.asarray(v)[e] if np.ndim(v) >= 1 and np.shape(v)[0] == self.nsys else v
                               for v in values] for e in range(self.nsys)]
-        self._probes, self._nsteps = None, 0
+        self._probes, self._recorders, self._nsteps = None, None, 0
 
     def step(self, dt):
         """One fixed step of every member (asynchronous: returns after the launches)."""
@@ -127,6 +128,8 @@ class Ensemble:
         self._nsteps += 1
         if self._probes is not None:
             self._record_probes()
+        if self._recorders is not None:
+            self._record_on(self._recorders)
 
     # ---- device probes (probes.py) ----------------------------------------------------
     def add_probe(self, name, expression, reduce="sum"):
@@ -152,7 +155,33 @@ class Ensemble:
         return self._probes.series() if self._probes is not None else {}
 
     def _record_probes(self):
-        self._probes.record(self.solver, self.cur, self.t, self._nsteps, self._x, self._member_pars)
+        self._record_on(self._probes)
+
+    def _record_on(self, series_set):
+        series_set.record(self.solver, self.cur, self.t, self._nsteps, self._x, self._member_pars)
+
+    # ---- device recorders (recorders.py) ----------------------------------------------
+    def add_recorder(self, name, expression, every=1, nodes=slice(None), pool="sample", capacity=None):
+        """Record ``expression`` at the columns ``nodes`` of every member (``Simulation.add_recorder``),
+        now and after every ``every``-th ``step``; ``recorders[name] = (t, x, values[rows, nsys, ncols])``,
+        ``x [nsys, ncols]`` when the members have grids of their own.  This rank's members only."""
+        if self._recorders is None:
+            self._recorders = RecorderSet(self.model, self.N)
+        self._recorders.add(name, expression, every, nodes, pool, capacity)
+        try:
+            self._record_on(self._recorders)
+        except Exception:
+            self._recorders.remove(name)
+            raise
+
+    def remove_recorder(self, name):
+        if self._recorders is None:
+            raise KeyError(name)
+        self._recorders.remove(name)
+
+    @property
+    def recorders(self):
+        return self._recorders.series() if self._recorders is not None else {}
 
     def restart(self):
         """Back to the initial state and t = 0 (parameters, hook and factorisation plan stay; a
@@ -176,6 +205,8 @@ class Ensemble:
     def close(self):
         if self._probes is not None:
             self._probes.close()
+        if self._recorders is not None:
+            self._recorders.close()
         self.solver.close()
 
     def state(self):

@@ -37,6 +37,7 @@ from numpy import isclose
 from . import schemes
 from .device import DirichletHook, null_hook, stepper_for
 from .probes import ProbeSet
+from .recorders import RecorderSet
 
 __all__ = ["Simulation", "PostProcess", "Stream", "Timer"]
 
@@ -105,6 +106,7 @@ class Simulation:
         self._hook = hook
         self._container = None
         self._probes = None
+        self._recorders = None
         self._iterator = self.compute()
 
     def _compute_one_step(self, t, fields, pars):
@@ -137,6 +139,8 @@ class Simulation:
                 self.t, self.fields, self.parameters = t, fields, pars
                 if self._probes is not None:
                     self._record_probes()
+                if self._recorders is not None:
+                    self._record_on(self._recorders)
                 for pprocess in self.post_processes:
                     pprocess.function(self)
                 self.stream.emit(self)
@@ -254,14 +258,48 @@ class Simulation:
         return self._probes.series(per_system=False) if self._probes is not None else {}
 
     def _record_probes(self):
+        self._record_on(self._probes)
+
+    def _record_on(self, series_set):
         # the prologue of the device schemes (schemes._device_step): a state that is not resident is
         # uploaded, one that is stays where it is
         fields, pars = self.fields, self.parameters
         stepper = stepper_for(self.model, fields, pars)
         stepper.bind(fields, pars)
         slot = stepper.acquire(fields)
-        self._probes.record(stepper.solver, slot, self.t, self.i, np.asarray(fields["x"]),
-                            [[pars[k] for k in stepper.compiled.pars]])
+        series_set.record(stepper.solver, slot, self.t, self.i, np.asarray(fields["x"]),
+                          [[pars[k] for k in stepper.compiled.pars]])
+
+    # ---- device recorders (recorders.py) ----------------------------------------------
+    def add_recorder(self, name, expression, every=1, nodes=slice(None), pool="sample", capacity=None):
+        """Record the model expression ``expression`` on the GPU at the columns ``nodes`` (a slice; a
+        column is the ``pool`` -- "sample", "max", "min", "mean" -- of a bin of ``nodes.step`` nodes):
+        a row now, then after every ``every``-th step, where the post-processes run.  The series is
+        ``recorders[name] = (t, x, values[rows, ncols])``; the fields never come to the host for it."""
+        if self._recorders is None:
+            self._recorders = RecorderSet(self.model, np.asarray(self.fields["x"]).size)
+        self._recorders.add(name, expression, every, nodes, pool, capacity)
+        try:
+            self._record_on(self._recorders)
+        except Exception:
+            self._recorders.remove(name)       # (not kept, as a probe that cannot run: the others go on)
+            raise
+
+    def remove_recorder(self, name):
+        if self._recorders is None:
+            raise KeyError(name)
+        self._recorders.remove(name)
+
+    @property
+    def recorders(self):
+        """name -> (t, x, values): float64 arrays, one row of values per recorded state."""
+        return self._recorders.series(per_system=False) if self._recorders is not None else {}
+
+    def save_recorder(self, name, path):
+        """The series of recorder ``name`` as a container directory that ``retrieve_container`` reads."""
+        if self._recorders is None:
+            raise KeyError(name)
+        return self._recorders.save(name, path, self.parameters)
 
     def __iter__(self):
         return self.compute()

@@ -3,21 +3,8 @@
 // do on the GPU, the shuffle / LDS trees of tfk_probe_partial / tfk_probe_final are replayed in
 // their order (64-lane xor tree, four wavefronts of 256-thread workgroups; one wavefront per probe in
 // tfk_probe_final).  Built per probe set
-// by tests/probe_host/build_probe_host.py; never part of libtriflow_hip.so.
-#include <cmath>
-#include <cstdint>
-#include <vector>
-
-#define TF_DEVICE static inline
-#define TF_DEVICE_M inline
-#include "tf_args.h"
-#include "tf_math.h"
-using std::sqrt; using std::exp; using std::log; using std::sin; using std::cos; using std::tan;
-using std::tanh; using std::sinh; using std::cosh; using std::pow; using std::atan; using std::asin;
-using std::acos; using std::log10; using std::log2; using std::cbrt; using std::expm1; using std::log1p;
-using std::floor; using std::ceil;
-#include TF_PROBE_HOST_HEADER
-#include "tf_kernels.h"
+// by tests/probe_host/build_probe_host.py on tests/observer_host; never part of libtriflow_hip.so.
+#include "observer_host.h"
 #include "tf_probe.h"
 
 namespace {
@@ -53,8 +40,8 @@ int probe_host_run(const TfLayout* Lp, const double* fields, const double* helpe
     const int nblk = (L.P + 255) / 256, nseg = (L.M + TF_PROBE_SEG - 1) / TF_PROBE_SEG, nb = nblk * nseg;
     std::vector<double> partial((size_t)L.nsys * TF_NPROBE * nb * 2), ends((size_t)L.nsys * TF_NPROBE * 2);
     TfProbeArgs a{};
-    a.L = L; a.fields = fields; a.helpers = helpers; a.parvec = parvec; a.parsca = parsca; a.dx = dx;
-    a.xcoord = xcoord; a.hc = hc; a.partial = partial.data(); a.ends = ends.data(); a.nblk = nblk; a.nseg = nseg;
+    static_cast<TfNodeArgs&>(a) = host_node_args(Lp, fields, helpers, parvec, parsca, dx, xcoord, hc);
+    a.partial = partial.data(); a.ends = ends.data(); a.nblk = nblk; a.nseg = nseg;
     for (int e = 0; e < L.nsys; ++e) {
         for (int sb = 0; sb < nb; ++sb) {                             // tfk_probe_partial
             const int sg = sb / nblk, b = sb - sg * nblk;

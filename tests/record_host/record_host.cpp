@@ -3,21 +3,7 @@
 // GPU, the parts of a bin meet in the order tfk_record combines them in (tf_record_finish over the
 // parts of a workgroup's LDS).  Built per recorder set by tests/record_host/build_record_host.py;
 // never part of libtriflow_hip.so.
-#include <cmath>
-#include <cstdint>
-#include <vector>
-
-#define TF_DEVICE static inline
-#define TF_DEVICE_M inline
-#include "tf_args.h"
-#include "tf_math.h"
-using std::sqrt; using std::exp; using std::log; using std::sin; using std::cos; using std::tan;
-using std::tanh; using std::sinh; using std::cosh; using std::pow; using std::atan; using std::asin;
-using std::acos; using std::log10; using std::log2; using std::cbrt; using std::expm1; using std::log1p;
-using std::floor; using std::ceil;
-#include TF_RECORD_HOST_HEADER
-#include "tf_kernels.h"
-#include "tf_probe.h"
+#include "observer_host.h"
 #include "tf_record.h"
 
 extern "C" {
@@ -29,8 +15,8 @@ int record_host_run(const TfLayout* Lp, const double* fields, const double* help
                     const double* parsca, const double* dx, const double* xcoord, const double* hc,
                     int which, int pool, int start, int stop, int step, double* out) {
     TfRecordArgs a{};
-    a.L = *Lp; a.fields = fields; a.helpers = helpers; a.parvec = parvec; a.parsca = parsca; a.dx = dx;
-    a.xcoord = xcoord; a.hc = hc; a.which = which; a.pool = pool; a.start = start; a.stop = stop; a.step = step;
+    static_cast<TfNodeArgs&>(a) = host_node_args(Lp, fields, helpers, parvec, parsca, dx, xcoord, hc);
+    a.which = which; a.pool = pool; a.start = start; a.stop = stop; a.step = step;
     a.ncols = (stop - start + step - 1) / step;
     a.split = 1;
     if (pool != TF_REC_SAMPLE)

@@ -504,22 +504,26 @@ class DeviceSolver:
         return out
 
 
-class DeviceProbe:
-    """``tf_probe``: the probe kernels of one probe set bound to one solver, and their ring."""
+class _DeviceObserver:
+    """What ``tf_probe`` and ``tf_record`` share: a code object of expressions bound to one solver, the
+    x plane and the host constants of the expressions.  ``_prefix``: of the C entry points, ``_noun``:
+    what the error message calls the set."""
 
-    def __init__(self, solver, code, kinds, nconst, capacity=1024):
+    _prefix = _noun = None
+
+    def _create(self, solver, code, nconst, *args):
+        """``<prefix>_create(solver, code, size, *args, &handle)``"""
         self.solver, self.lib = solver, solver.lib
-        self.nprobe, self.nconst, self.capacity = len(kinds), int(nconst), int(capacity)
+        self.nconst = int(nconst)
         self._code = C.create_string_buffer(code, len(code))
-        k = np.ascontiguousarray(kinds, dtype=np.int32)
         handle = C.c_void_p()
-        self.lib.call("tf_probe_create", solver.handle, C.cast(self._code, C.c_void_p), len(code),
-                      self.nprobe, k.ctypes.data_as(c_int32_p), self.nconst, self.capacity, C.byref(handle))
+        self.lib.call(self._prefix + "_create", solver.handle, C.cast(self._code, C.c_void_p), len(code),
+                      *args, C.byref(handle))
         self.handle = handle
 
     def close(self):
         if self.handle:
-            self.lib.dll.tf_probe_destroy(self.handle)
+            getattr(self.lib.dll, self._prefix + "_destroy")(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -529,96 +533,77 @@ class DeviceProbe:
             pass
 
     def _check_open(self):
-        # (the tf_probe reads its solver's layout, stream and planes: not after the solver is gone)
+        # (the handle reads its solver's layout, stream and planes: not after the solver is gone)
         if not self.solver.handle:
-            raise RuntimeError("the solver of this probe set was closed (rows not fetched before are lost)")
+            raise RuntimeError("the solver of this %s set was closed (rows not fetched before are lost)" % self._noun)
+
+    def _call(self, name, *args):
+        self._check_open()
+        self.lib.call("%s_%s" % (self._prefix, name), self.handle, *args)
 
     def set_consts(self, values):
-        """``values``: [nsys][nconst] host constants of the probe expressions."""
+        """``values``: [nsys][nconst] host constants of the expressions."""
         self._check_open()
         v = _f64(values).reshape(self.solver.nsys, self.nconst)
-        self.lib.call("tf_probe_set_consts", self.handle, _dptr(v) if v.size else None, self.nconst)
+        self._call("set_consts", _dptr(v) if v.size else None, self.nconst)
 
     def set_x(self, x):
         self._check_open()
         a = _f64(np.broadcast_to(np.asarray(x, dtype=float), (self.solver.nsys, self.solver.N)))
-        self.lib.call("tf_probe_set_x", self.handle, _dptr(a))
+        self._call("set_x", _dptr(a))
+
+    def _pending(self, *which):
+        n = C.c_int64(0)
+        self._call("pending", *which, C.byref(n))
+        return n.value
+
+    def _fetch(self, ncols, *which):
+        """Every row recorded since the last fetch, ``[rows][nsys][ncols]``."""
+        n = self._pending(*which)
+        out = np.empty((n, self.solver.nsys, ncols))
+        got = C.c_int64(0)
+        self._call("fetch", *which, _dptr(out), n, C.byref(got))
+        return out[:got.value]
+
+
+class DeviceProbe(_DeviceObserver):
+    """``tf_probe``: the probe kernels of one probe set bound to one solver, and their ring."""
+
+    _prefix, _noun = "tf_probe", "probe"
+
+    def __init__(self, solver, code, kinds, nconst, capacity=1024):
+        self.nprobe, self.capacity = len(kinds), int(capacity)
+        k = np.ascontiguousarray(kinds, dtype=np.int32)
+        self._create(solver, code, nconst, self.nprobe, k.ctypes.data_as(c_int32_p), int(nconst), self.capacity)
 
     def record(self, slot):
-        self._check_open()
-        self.lib.call("tf_probe_record", self.handle, int(slot))
+        self._call("record", int(slot))
 
     def pending(self):
-        self._check_open()
-        n = C.c_int64(0)
-        self.lib.call("tf_probe_pending", self.handle, C.byref(n))
-        return n.value
+        return self._pending()
 
     def fetch(self):
         """Every row recorded since the last fetch, ``[rows][nsys][nprobe]`` (waits for the stream)."""
-        n = self.pending()
-        out = np.empty((n, self.solver.nsys, self.nprobe))
-        got = C.c_int64(0)
-        self.lib.call("tf_probe_fetch", self.handle, _dptr(out), n, C.byref(got))
-        return out[:got.value]
+        return self._fetch(self.nprobe)
 
 
-class DeviceRecord:
+class DeviceRecord(_DeviceObserver):
     """``tf_record``: the record kernel of one recorder set bound to one solver, and the rings."""
+
+    _prefix, _noun = "tf_record", "recorder"
 
     def __init__(self, solver, code, geometry, nconst):
         """``geometry``: per recorder ``(expression, pool, start, stop, step, rows of the ring)``."""
-        self.solver, self.lib = solver, solver.lib
-        self.nconst = int(nconst)
         g = np.ascontiguousarray(geometry, dtype=np.int32).reshape(-1, 6)
         self.ncols = [-(-(int(r[3]) - int(r[2])) // int(r[4])) for r in g]
-        self._code = C.create_string_buffer(code, len(code))
-        handle = C.c_void_p()
-        self.lib.call("tf_record_create", solver.handle, C.cast(self._code, C.c_void_p), len(code),
-                      len(g), g.ctypes.data_as(c_int32_p), self.nconst, C.byref(handle))
-        self.handle = handle
-
-    def close(self):
-        if self.handle:
-            self.lib.dll.tf_record_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check_open(self):
-        # (the tf_record reads its solver's layout, stream and planes: not after the solver is gone)
-        if not self.solver.handle:
-            raise RuntimeError("the solver of this recorder set was closed (rows not fetched before are lost)")
-
-    def set_consts(self, values):
-        """``values``: [nsys][nconst] host constants of the record expressions."""
-        self._check_open()
-        v = _f64(values).reshape(self.solver.nsys, self.nconst)
-        self.lib.call("tf_record_set_consts", self.handle, _dptr(v) if v.size else None, self.nconst)
-
-    def set_x(self, x):
-        self._check_open()
-        a = _f64(np.broadcast_to(np.asarray(x, dtype=float), (self.solver.nsys, self.solver.N)))
-        self.lib.call("tf_record_set_x", self.handle, _dptr(a))
+        self._create(solver, code, nconst, len(g), g.ctypes.data_as(c_int32_p), int(nconst))
 
     def record(self, which, slot):
-        self._check_open()
-        self.lib.call("tf_record_record", self.handle, int(which), int(slot))
+        self._call("record", int(which), int(slot))
 
     def pending(self, which):
-        self._check_open()
-        n = C.c_int64(0)
-        self.lib.call("tf_record_pending", self.handle, int(which), C.byref(n))
-        return n.value
+        return self._pending(int(which))
 
     def fetch(self, which):
         """Every row of recorder ``which`` recorded since its last fetch, ``[rows][nsys][ncols]``."""
-        n = self.pending(which)
-        out = np.empty((n, self.solver.nsys, self.ncols[which]))
-        got = C.c_int64(0)
-        self.lib.call("tf_record_fetch", self.handle, int(which), _dptr(out), n, C.byref(got))
-        return out[:got.value]
+        return self._fetch(self.ncols[which], int(which))

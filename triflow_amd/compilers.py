@@ -51,7 +51,8 @@ HIPCC_FLAGS = [*os.environ.get("TRIFLOW_HIPCC_OPT", "-O3").split(), "-std=c++17"
 #: translation units of the host runtime (see the header of csrc/tf_solver.h)
 RUNTIME_SOURCES = ("tf_rt_plan.cpp", "tf_rt_io.cpp", "tf_rt_steps.cpp", "tf_rt_diag.cpp",
                    "tf_solver_sweeps.cpp", "tf_solver_linear.cpp", "tf_rt_probe.cpp", "tf_rt_record.cpp")
-_SKELETON = ("tf_args.h", "tf_math.h", "tf_kernels.h", "tf_crs.h", "tf_coop_hip.h", "tf_cr2_hip.h", "tf_cr3_hip.h", "tf_probe.h", "tf_record.h", "tf_entry_hip.h")
+_SKELETON = ("tf_args.h", "tf_math.h", "tf_kernels.h", "tf_crs.h", "tf_coop_hip.h", "tf_cr2_hip.h", "tf_cr3_hip.h",
+             "tf_node.h", "tf_probe.h", "tf_record.h", "tf_entry_hip.h")
 _TU_HEAD = ('#include <hip/hip_runtime.h>\n'
             '#define TF_DEVICE __device__ __forceinline__\n'
             '%s'
@@ -118,11 +119,11 @@ def resource_usage(hsaco_path):
         return json.load(f)["kernels"]
 
 
-def _compile_code_object(model, source, tag, hsaco, probes=False):
+def _compile_code_object(model, source, tag, hsaco, observer=None):
     """hipcc on the generated translation unit -> ``hsaco`` (+ source and resource table next to it).
-    ``probes``: the unit carries a probe block (build_probe_code_object) or, ``"record"``, a record block
-    (build_record_code_object); only the probe / record kernels of that object are ever launched, so
-    there is no second build for the spill gate -- a probe / record kernel that spills is refused instead."""
+    ``observer``: the unit carries an observer's block (build_observer_code_object) and this is its kind,
+    "probe" or "record": only the kernels ``tfk_<kind>*`` of that object are ever launched, so there is
+    no second build for the spill gate -- one of them that spills is refused instead."""
     global BUILD_COUNT
     BUILD_COUNT += 1
     hip = os.path.join(CACHE_DIR, "model_%s.hip" % tag)
@@ -147,15 +148,13 @@ def _compile_code_object(model, source, tag, hsaco, probes=False):
     flags = list(HIPCC_FLAGS)
     usage = compile_with(flags, tmp)
     spilled = sorted(k for k, u in usage.items() if u.get("ScratchSize", 0) > 0)
-    if probes:
-        what = "record" if probes == "record" else "probe"
-        spilled_probe = [k for k in spilled if k.startswith("tfk_" + what)]
-        if spilled_probe:
+    if observer:
+        spilled = [k for k in spilled if k.startswith("tfk_" + observer)]
+        if spilled:
             os.remove(tmp)
             raise codegen.UnsupportedExpression(
                 "the %s kernels (%s) need more registers than a wavefront has: "
-                "use fewer or simpler %ss" % (what, ", ".join(spilled_probe), what))
-        spilled = []
+                "use fewer or simpler %ss" % (observer, ", ".join(spilled), observer))
     alt_flags, alt_usage = None, None
     alt = hsaco[:-len(".hsaco")] + ".alt.hsaco"
     if spilled and "-O1" not in flags and "-O0" not in flags \
@@ -212,7 +211,7 @@ def alternate_of(hsaco_path):
     return (alt, kernels) if kernels and os.path.exists(alt) else (None, [])
 
 
-def _build_locked(model, source, tag, hsaco, probes=False):
+def _build_locked(model, source, tag, hsaco, observer=None):
     """Compile ``source`` into ``hsaco`` unless it is in the cache already."""
     if os.path.exists(hsaco):
         return
@@ -229,7 +228,7 @@ def _build_locked(model, source, tag, hsaco, probes=False):
                 pass
             try:
                 if not os.path.exists(hsaco):
-                    _compile_code_object(model, source, tag, hsaco, probes)
+                    _compile_code_object(model, source, tag, hsaco, observer)
             finally:
                 try:
                     fcntl.flock(lock, fcntl.LOCK_UN)
@@ -259,29 +258,19 @@ def build_code_object(model, parvec_mask=0, seg=None, sweep_block=None):
     return hsaco, spec
 
 
-def build_probe_code_object(model, probe_block, parvec_mask=0, seg=8, sweep_block=256):
-    """The model's translation unit followed by a probe block (codegen.lower_probes) -> path of the
-    cached code object.  Same parameter layout and sweep segment as the solver's own code object:
-    the probe kernels read that solver's planes and parameter slots."""
+def build_observer_code_object(model, block, kind, parvec_mask=0, seg=8, sweep_block=256):
+    """The model's translation unit followed by the block of an observer of ``kind`` "probe"
+    (codegen.lower_probes) or "record" (codegen.lower_records) -> path of the cached code object, of which
+    only the kernels ``tfk_<kind>*`` are launched.  Same parameter layout and sweep segment as the solver's
+    own code object: the observer's kernels read that solver's planes and parameter slots."""
+    if kind not in ("probe", "record"):
+        raise ValueError("unknown kind of observer %r" % (kind,))
     body, _ = codegen.lower_model(model, parvec_mask=parvec_mask, seg=seg, sweep_block=sweep_block)
-    source = _TU_HEAD % "" + body + probe_block + _TU_TAIL
-    tag = codegen.source_hash(source, _skeleton_stamp(), " ".join(HIPCC_FLAGS), hipcc_version(), "probe", "elf")
+    source = _TU_HEAD % "" + body + block + _TU_TAIL
+    tag = codegen.source_hash(source, _skeleton_stamp(), " ".join(HIPCC_FLAGS), hipcc_version(), kind, "elf")
     os.makedirs(CACHE_DIR, exist_ok=True)
     hsaco = os.path.join(CACHE_DIR, "model_%s.hsaco" % tag)
-    _build_locked(model, source, tag, hsaco, probes=True)
-    return hsaco
-
-
-def build_record_code_object(model, record_block, parvec_mask=0, seg=8, sweep_block=256):
-    """The model's translation unit followed by a record block (codegen.lower_records) -> path of the
-    cached code object, of which only tfk_record is launched (recorders.py).  Same parameter layout and
-    sweep segment as the solver's own code object, as for the probes."""
-    body, _ = codegen.lower_model(model, parvec_mask=parvec_mask, seg=seg, sweep_block=sweep_block)
-    source = _TU_HEAD % "" + body + record_block + _TU_TAIL
-    tag = codegen.source_hash(source, _skeleton_stamp(), " ".join(HIPCC_FLAGS), hipcc_version(), "record", "elf")
-    os.makedirs(CACHE_DIR, exist_ok=True)
-    hsaco = os.path.join(CACHE_DIR, "model_%s.hsaco" % tag)
-    _build_locked(model, source, tag, hsaco, probes="record")
+    _build_locked(model, source, tag, hsaco, observer=kind)
     return hsaco
 
 

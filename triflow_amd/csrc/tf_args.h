@@ -326,6 +326,20 @@ struct TfTopArgs {                 // final 1-node system per ensemble member
 // ... and of a level that is ONE chunk per system (a 1 x 1 block's records fit the LDS twice as long)
 #define TF_CRS_TOPLEN(b) ((b) == 1 ? 512 : 256)
 
+// The node core (tf_node.h) of the device observers -- probes and recorders: what it takes to evaluate
+// a model expression at the nodes of a resident state slot.  The base (first bytes) of the arguments of every
+// observer kernel; the host runtime fills it in one place (tf_observer, tf_solver.h).
+struct TfNodeArgs {
+    TfLayout L;
+    const double* fields;          // [nvar] planes: the state slot observed
+    const double* helpers;         // [nh] planes
+    const double* parvec;          // [npar] planes (only those flagged vector are read)
+    const double* parsca;          // [npar][nsys] the solver's scalar parameters (+ the model's host constants)
+    const double* dx;              // [nsys]
+    const double* xcoord;          // 1 plane: x (the solver's when its model reads x, else the observer's own)
+    const double* hc;              // [nhc][nsys] host constants of the observer's expressions
+};
+
 // Device probes (tf_probe.h, tf_rt_probe.cpp): reductions of model expressions over the nodes of every
 // system, evaluated on a resident state slot.  tfk_probe_partial: grid (nsys * nblk, nseg), one thread per
 // segment of TF_PROBE_SEG nodes of a level-1 chunk, one partial per workgroup, probe and system;
@@ -342,15 +356,7 @@ struct TfTopArgs {                 // final 1-node system per ensemble member
 // nodes per thread of tfk_probe_partial: one thread per whole chunk left most of the GPU idle (config 3:
 // 31 250 chunks of 32 nodes, 14.8 us for 24 MB); segments of 8 as in the F sweep (TF_SEG)
 #define TF_PROBE_SEG 8
-struct TfProbeArgs {
-    TfLayout L;
-    const double* fields;          // [nvar] planes: the state slot probed
-    const double* helpers;         // [nh] planes
-    const double* parvec;          // [npar] planes (only those flagged vector are read)
-    const double* parsca;          // [npar][nsys] the solver's scalar parameters (+ the model's host constants)
-    const double* dx;              // [nsys]
-    const double* xcoord;          // 1 plane: x (the solver's when its model reads x, else the probe's own)
-    const double* hc;              // [nhc][nsys] host constants of the probe expressions
+struct TfProbeArgs : TfNodeArgs {
     double* partial;               // [nsys][nprobe][nseg * nblk] (value, natural index) pairs
     double* ends;                  // [nsys][nprobe][2]: f at natural nodes 0 and N-1 (integral)
     int nblk;                      // workgroups of tfk_probe_partial per system and segment row
@@ -370,15 +376,7 @@ struct TfProbeArgs {
 #define TF_REC_MEAN 3              // sum in a fixed order / the bin's node count
 // threads of a workgroup of tfk_record; `split` of them share a bin (a power of two <= TF_REC_BLOCK)
 #define TF_REC_BLOCK 256
-struct TfRecordArgs {
-    TfLayout L;
-    const double* fields;          // [nvar] planes: the state slot recorded
-    const double* helpers;         // [nh] planes
-    const double* parvec;          // [npar] planes (only those flagged vector are read)
-    const double* parsca;          // [npar][nsys] the solver's scalar parameters (+ the model's host constants)
-    const double* dx;              // [nsys]
-    const double* xcoord;          // 1 plane: x (the solver's when its model reads x, else the recorder's own)
-    const double* hc;              // [nhc][nsys] host constants of the record expressions
+struct TfRecordArgs : TfNodeArgs {
     int which;                     // expression of the record block (tf_eval_record's first argument)
     int pool;                      // TF_REC_*
     int start, stop, step;         // the window of nodes (slice.indices(N), step >= 1)
@@ -390,6 +388,11 @@ struct TfRecordArgs {
     int* cursor;                   // [0]: next row of the ring (wraps at capacity), [1]: workgroups done with it
     double* ring;                  // [capacity][nsys][ncols]
 };
+// (passed by value to kernels of code objects the host did not compile: the bytes are the contract)
+// (the base comes first and the members follow in their order: the sizes pin the bytes)
+static_assert(sizeof(TfNodeArgs) == 96, "TfNodeArgs changed its layout");
+static_assert(sizeof(TfProbeArgs) == 144, "TfProbeArgs changed its layout");
+static_assert(sizeof(TfRecordArgs) == 152, "TfRecordArgs changed its layout");
 
 // Kernel table: index = launch id used by the runtime, name = entry point in
 // the per-model code object (tf_entry_hip.h).  New entries go at the end: the

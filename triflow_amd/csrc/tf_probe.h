@@ -8,9 +8,11 @@
 // the no-op defaults below (every code object holds every kernel of the table, tf_args.h).
 //
 // This file holds what the host harness of the test suite (tests/probe_host/) also compiles
-// with g++: the reduction algebra and the walk of one thread along its chunk.  The shuffle /
-// LDS trees and the ring hand-over are in tf_entry_hip.h (tfk_probe_partial, tfk_probe_final).
+// with g++: the reduction algebra and the walk of one thread along its chunk, on the node window
+// that the probes share with the recorders (tf_node.h).  The shuffle / LDS trees and the ring
+// hand-over are in tf_entry_hip.h (tfk_probe_partial, tfk_probe_final).
 #pragma once
+#include "tf_node.h"
 
 #ifndef TF_NPROBE
 #define TF_NPROBE 0
@@ -23,8 +25,8 @@ TF_DEVICE void tf_eval_probe(const double (&)[TF_NVAR + TF_NH][2 * TF_MP + 1], c
 #define TF_NPROBE_A (TF_NPROBE > 0 ? TF_NPROBE : 1)
 
 // Running state of one reduction: the value and, for argmax / argmin, the natural node index it was
-// met at (a double: exact for any node count a plane can hold).  Sums ignore the index.
-struct TfProbeAcc { double v, i; };
+// met at.  Sums ignore the index.
+typedef TfNodeAcc TfProbeAcc;
 
 TF_DEVICE bool tf_probe_summed(int kind) { return kind <= TF_PROBE_INTEGRAL; }
 
@@ -35,19 +37,14 @@ TF_DEVICE TfProbeAcc tf_probe_identity(int kind) {
     return {up ? -inf : inf, inf};
 }
 
-// b after a: the reduction of the two.  Maxima / minima follow numpy: NaN wins (max, min), the
-// first NaN wins (argmax, argmin), among equal values the smallest node index wins.  For every
+// b after a: the reduction of the two.  Maxima / minima follow numpy: NaN wins (max, min: tf_node_extremum),
+// the first NaN wins (argmax, argmin), among equal values the smallest node index wins.  For every
 // kind but the sums the result does not depend on the order of the operands, so any tree gives
 // numpy's answer; the sums are added in a fixed order (the trees of tf_entry_hip.h).
 TF_DEVICE TfProbeAcc tf_probe_combine(int kind, TfProbeAcc a, TfProbeAcc b) {
     if (tf_probe_summed(kind)) return {a.v + b.v, 0.0};
     const bool anan = a.v != a.v, bnan = b.v != b.v;
-    if (kind == TF_PROBE_MAX || kind == TF_PROBE_MIN) {
-        if (anan) return a;
-        if (bnan) return b;
-        const bool take = kind == TF_PROBE_MAX ? b.v > a.v : b.v < a.v;
-        return take ? b : a;
-    }
+    if (kind == TF_PROBE_MAX || kind == TF_PROBE_MIN) return tf_node_extremum(kind == TF_PROBE_MAX, a, b);
     bool take;
     if (anan) take = bnan && b.i < a.i;
     else if (bnan) take = true;
@@ -69,56 +66,29 @@ TF_DEVICE double tf_probe_finish(int kind, TfProbeAcc r, int N, int periodic, do
     }
 }
 
-// One thread, segment sg (TF_PROBE_SEG nodes) of chunk p of system e: the register window slides along
-// the segment as in the F sweep (tfk_sweep_body: ghosts through tf_nbr, wrapped or clamped at the ends
-// of the system), every node's probe values are folded into acc in node order.  The chunks that own natural nodes 0 and
-// N-1 also leave f there in a.ends (the integral's end correction).  NODES (the host harness of the
-// tests only): every node's values also go to nodes[(k * nsys + e) * N + natural index].
+// One thread, segment sg (TF_PROBE_SEG nodes) of chunk p of system e: the node window (tf_node.h) slides
+// along the segment, every node's probe values are folded into acc in node order.  The chunks that own
+// natural nodes 0 and N-1 also leave f there in a.ends (the integral's end correction).  NODES (the host
+// harness of the tests only): every node's values also go to nodes[(k * nsys + e) * N + natural index].
 template <bool NODES = false>
 TF_DEVICE void tf_probe_walk(const TfProbeArgs& a, int e, int p, int sg, TfProbeAcc (&acc)[TF_NPROBE_A],
                              double* nodes = nullptr) {
     const TfLayout& L = a.L;
-    const int pg = e * L.P + p;
     const int len = tf_len(L, p);
     const int gstart = tf_start(L, p);
     const int i0 = sg * TF_PROBE_SEG;
-    double par[TF_NPAR > 0 ? TF_NPAR : 1];
-#pragma unroll
-    for (int k = 0; k < TF_NPAR; ++k) par[k] = tf_par_is_vec[k] ? 0.0 : a.parsca[k * L.nsys + e];
-    double hc[TF_NPROBE_HC > 0 ? TF_NPROBE_HC : 1];
-#pragma unroll
-    for (int k = 0; k < TF_NPROBE_HC; ++k) hc[k] = a.hc[k * L.nsys + e];
-    const double dx = a.dx[e];
-    auto ld = [&](int f, int ii) -> double {
-        const int64_t s = (ii >= 0 && ii < len) ? tf_idx(L, pg, ii) : tf_nbr(L, e, p, len, 0, ii);
-        return f >= TF_NVAR ? a.helpers[(int64_t)(f - TF_NVAR) * L.plane + s]
-                            : a.fields[(int64_t)f * L.plane + s];
-    };
+    TfNodeWindow<TF_NPROBE_HC, TF_PROBE_USES_X> W(a, e);
 #pragma unroll
     for (int k = 0; k < TF_NPROBE_A; ++k) acc[k] = tf_probe_identity(tf_probe_kind[k]);
     if (i0 >= len) return;
-    double w[TF_NVAR + TF_NH][2 * TF_MP + 1];
-#pragma unroll
-    for (int f = 0; f < TF_NVAR + TF_NH; ++f)
-#pragma unroll
-        for (int o = 1; o < 2 * TF_MP + 1; ++o) w[f][o] = ld(f, i0 + o - 1 - TF_MP);
+    W.prime(p, len, i0);
 #pragma unroll
     for (int j = 0; j < TF_PROBE_SEG; ++j) {
         const int i = i0 + j;
         if (i >= len) break;
-#pragma unroll
-        for (int f = 0; f < TF_NVAR + TF_NH; ++f) {
-#pragma unroll
-            for (int o = 0; o < 2 * TF_MP; ++o) w[f][o] = w[f][o + 1];
-            w[f][2 * TF_MP] = ld(f, i + TF_MP);
-        }
-        const int64_t s = tf_idx(L, pg, i);
-#pragma unroll
-        for (int k = 0; k < TF_NPAR; ++k)
-            if (tf_par_is_vec[k]) par[k] = a.parvec[(int64_t)k * L.plane + s];
-        const double xc = TF_PROBE_USES_X ? a.xcoord[s] : 0.0;
+        W.advance(p, len, i);
         double v[TF_NPROBE_A];
-        tf_eval_probe(w, par, hc, dx, xc, v);
+        tf_eval_probe(W.w, W.par, W.hc, W.dx, W.xc, v);
         const double gi = (double)(gstart + i);
 #pragma unroll
         for (int k = 0; k < TF_NPROBE; ++k) {

@@ -7,9 +7,10 @@
 // TF_REC_USES_X and tf_eval_record before this header is read; every other code object compiles the
 // no-op defaults below (every code object holds every kernel of the table, tf_args.h).
 //
-// The walk and the combine are what the host harness of the test suite (tests/record_host/) also
+// The walk (on the node window the recorders share with the probes, tf_node.h) and the combine are what the host harness of the test suite (tests/record_host/) also
 // compiles with g++; the kernel itself is at the end of the file.
 #pragma once
+#include "tf_node.h"
 
 #ifndef TF_NREC
 #define TF_NREC 0
@@ -19,12 +20,11 @@ TF_DEVICE double tf_eval_record(int, const double (&)[TF_NVAR + TF_NH][2 * TF_MP
                                 const double*, double, double) { return 0.0; }
 #endif
 
-// b after a.  Maxima / minima are the probes' operator (numpy's: NaN wins; the order of the operands
+// b after a.  Maxima / minima as numpy has them (tf_node_extremum: NaN wins; the order of the operands
 // does not matter), the mean's sum is added in the order the caller fixes.
 TF_DEVICE double tf_rec_combine(int pool, double a, double b) {
     if (pool == TF_REC_MEAN) return a + b;
-    return tf_probe_combine(pool == TF_REC_MAX ? TF_PROBE_MAX : TF_PROBE_MIN, TfProbeAcc{a, 0.0},
-                            TfProbeAcc{b, 0.0}).v;
+    return tf_node_extremum(pool == TF_REC_MAX, TfNodeAcc{a, 0.0}, TfNodeAcc{b, 0.0}).v;
 }
 
 // nodes of bin j ("sample": its first node only)
@@ -35,45 +35,19 @@ TF_DEVICE int tf_rec_count(const TfRecordArgs& a, int j) {
 }
 
 // One thread: the natural nodes g0 ... g0 + n - 1 (n >= 1, inside the system) of system e, folded in node
-// order.  The register window slides along the nodes as in the F sweep and in tf_probe_walk (ghosts
-// through tf_nbr, wrapped or clamped at the ends of the system); a walk that leaves its chunk goes on
-// at row 0 of the next one with the window it holds.
+// order.  The node window (tf_node.h) slides along them; a walk that leaves its chunk goes on at row 0 of
+// the next one with the window it holds.
 TF_DEVICE double tf_record_walk(const TfRecordArgs& a, int e, int g0, int n) {
     const TfLayout& L = a.L;
     int p, i;
     tf_locate(L, g0, p, i);
     int len = tf_len(L, p);
-    double par[TF_NPAR > 0 ? TF_NPAR : 1];
-#pragma unroll
-    for (int k = 0; k < TF_NPAR; ++k) par[k] = tf_par_is_vec[k] ? 0.0 : a.parsca[k * L.nsys + e];
-    double hc[TF_NREC_HC > 0 ? TF_NREC_HC : 1];
-#pragma unroll
-    for (int k = 0; k < TF_NREC_HC; ++k) hc[k] = a.hc[k * L.nsys + e];
-    const double dx = a.dx[e];
-    auto ld = [&](int f, int ii) -> double {
-        const int64_t s = (ii >= 0 && ii < len) ? tf_idx(L, e * L.P + p, ii) : tf_nbr(L, e, p, len, 0, ii);
-        return f >= TF_NVAR ? a.helpers[(int64_t)(f - TF_NVAR) * L.plane + s]
-                            : a.fields[(int64_t)f * L.plane + s];
-    };
-    double w[TF_NVAR + TF_NH][2 * TF_MP + 1];
-#pragma unroll
-    for (int f = 0; f < TF_NVAR + TF_NH; ++f)
-#pragma unroll
-        for (int o = 1; o < 2 * TF_MP + 1; ++o) w[f][o] = ld(f, i + o - 1 - TF_MP);
+    TfNodeWindow<TF_NREC_HC, TF_REC_USES_X> W(a, e);
+    W.prime(p, len, i);
     double acc = 0.0;
     for (int j = 0; j < n; ++j) {
-#pragma unroll
-        for (int f = 0; f < TF_NVAR + TF_NH; ++f) {
-#pragma unroll
-            for (int o = 0; o < 2 * TF_MP; ++o) w[f][o] = w[f][o + 1];
-            w[f][2 * TF_MP] = ld(f, i + TF_MP);
-        }
-        const int64_t s = tf_idx(L, e * L.P + p, i);
-#pragma unroll
-        for (int k = 0; k < TF_NPAR; ++k)
-            if (tf_par_is_vec[k]) par[k] = a.parvec[(int64_t)k * L.plane + s];
-        const double xc = TF_REC_USES_X ? a.xcoord[s] : 0.0;
-        const double v = tf_eval_record(a.which, w, par, hc, dx, xc);
+        W.advance(p, len, i);
+        const double v = tf_eval_record(a.which, W.w, W.par, W.hc, W.dx, W.xc);
         acc = j == 0 ? v : tf_rec_combine(a.pool, acc, v);
         if (++i == len && p + 1 < L.P) { ++p; i = 0; len = tf_len(L, p); }
     }

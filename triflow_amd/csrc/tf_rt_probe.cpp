@@ -1,21 +1,17 @@
 // Host runtime of libtriflow_hip: device probes (tf_probe_*).  A probe set is a second code object of
 // the solver's model -- the model's translation unit plus the generated probe block (codegen.lower_probes)
 // -- of which only tfk_probe_partial / tfk_probe_final are launched, on the solver's stream, on one of
-// its state slots.  The rows go into a ring in device memory; the host waits only when the ring is full
-// (one copy of all of it) and when the caller fetches.
+// its state slots (tf_observer, tf_solver.h: what the probes share with the recorders).  The rows go into
+// a ring in device memory; the host waits only when the ring is full (one copy of all of it) and when the
+// caller fetches.
 #include "tf_solver.h"
 
-struct tf_probe {
-    tf_solver* solver = nullptr;
-    tfb::Module* module = nullptr;
-    int nprobe = 0, capacity = 0, nhc = 0, nblk = 0, nseg = 0;
-    int64_t bytes = 0;
-    DevBuf hc, xplane, partial, ends, ring;    // ring: [0] row cursor + arrivals (2 ints), then the rows
-    bool own_x = false;                        // the solver holds no x plane (its model does not read x)
+struct tf_probe : tf_observer {
+    int nprobe = 0, capacity = 0, nblk = 0, nseg = 0;
+    DevBuf partial, ends, ring;                // ring: [0] row cursor + arrivals (2 ints), then the rows
     int on_device = 0;                         // rows queued since the ring was last emptied (host mirror)
     std::vector<double> host_rows;             // rows drained but not fetched yet, [row][nsys][nprobe]
     size_t row_size() const { return (size_t)solver->nsys * nprobe; }
-    ~tf_probe() { if (module) tfb::module_unload(module); }
 
     // the ring's rows to host_rows, one copy; the cursor goes back to row 0 (queued on the stream)
     void drain() {
@@ -34,19 +30,6 @@ struct tf_probe {
     }
 };
 
-namespace {
-void probe_launch(tf_probe* p, int kernel, unsigned gx, unsigned gy, const TfProbeArgs& a) {
-    tf_solver* s = p->solver;
-    if ((s->timing >> kernel) & 1ull) {          // (timed like the solver's own launches: tf_timing_get)
-        tf_solver::Stamp st{kernel, s->get_event(), s->get_event()};
-        tfb::launch_timed(p->module, kernel, gx, gy, 256, &a, sizeof(a), s->stream, st.a, st.b);
-        s->stamps.push_back(st);
-    } else {
-        tfb::launch(p->module, kernel, gx, gy, 256, &a, sizeof(a), s->stream);
-    }
-}
-}  // namespace
-
 extern "C" {
 
 int tf_probe_create(tf_solver* s, const void* code_object, size_t code_size, int32_t nprobe,
@@ -58,19 +41,12 @@ int tf_probe_create(tf_solver* s, const void* code_object, size_t code_size, int
     for (int k = 0; k < nprobe; ++k)
         require(kinds[k] >= 0 && kinds[k] < TF_PROBE_KINDS, "tf_probe_create: unknown reduction");
     std::unique_ptr<tf_probe> p(new tf_probe());
-    p->solver = s;
+    p->init(s, code_object, code_size, nconst);
     p->nprobe = nprobe;
     p->capacity = capacity;
-    p->nhc = nconst;
     p->nblk = (int)tf_solver::cdiv(s->L1.P, 256);
     p->nseg = (int)tf_solver::cdiv(s->L1.M, TF_PROBE_SEG);
-    p->module = tfb::module_load(code_object, code_size);
     const int nsys = s->nsys;
-    p->hc.alloc((size_t)std::max(nconst, 1) * nsys, p->bytes);
-    // x of the nodes (argmax / argmin, probes that read x): the solver's plane when its model reads x
-    // (bound with the other inputs, tf_set_x), else a plane of the probe's own (tf_probe_set_x)
-    p->own_x = !s->spec.uses_x;
-    if (p->own_x) p->xplane.alloc((size_t)s->L1.plane, p->bytes);
     p->partial.alloc((size_t)nsys * nprobe * p->nseg * p->nblk * 2, p->bytes);
     p->ends.alloc((size_t)nsys * nprobe * 2, p->bytes);
     p->ring.alloc(1 + (size_t)capacity * nsys * nprobe, p->bytes);      // (zero-filled: cursor 0)
@@ -83,19 +59,14 @@ void tf_probe_destroy(tf_probe* p) { delete p; }
 int tf_probe_set_consts(tf_probe* p, const double* values, int32_t nconst) {
     TF_API_BEGIN
     require(p && (values || nconst == 0), "null argument");
-    require(nconst == p->nhc, "tf_probe_set_consts: constant count differs from tf_probe_create");
-    const int nsys = p->solver->nsys;
-    std::vector<double> t((size_t)std::max(nconst, 1) * nsys, 0.0);    // [nsys][nconst] -> [nconst][nsys]
-    for (int e = 0; e < nsys; ++e)
-        for (int k = 0; k < nconst; ++k) t[(size_t)k * nsys + e] = values[(size_t)e * nconst + k];
-    tfb::h2d(p->hc.p, t.data(), t.size() * sizeof(double), p->solver->stream);
+    p->set_consts("tf_probe", values, nconst);
     TF_API_END
 }
 
 int tf_probe_set_x(tf_probe* p, const double* x) {
     TF_API_BEGIN
     require(p && x, "null argument");
-    if (p->own_x) p->solver->upload_planes(x, p->xplane.p, 1);
+    p->set_x(x);
     TF_API_END
 }
 
@@ -106,14 +77,7 @@ int tf_probe_record(tf_probe* p, int32_t slot) {
     if (p->on_device == p->capacity) p->drain();
     TfProbeArgs a;
     std::memset(&a, 0, sizeof a);
-    a.L = s->L1;
-    a.fields = s->st(slot);
-    a.helpers = s->helpers.p;
-    a.parvec = s->parvec.p;
-    a.parsca = s->parsca.p;
-    a.dx = s->dx.p;
-    a.xcoord = p->own_x ? p->xplane.p : s->xcoord.p;
-    a.hc = p->hc.p;
+    static_cast<TfNodeArgs&>(a) = p->node_args(slot);
     a.partial = p->partial.p;
     a.ends = p->ends.p;
     a.nblk = p->nblk;
@@ -121,8 +85,8 @@ int tf_probe_record(tf_probe* p, int32_t slot) {
     a.capacity = p->capacity;
     a.cursor = (int*)p->ring.p;
     a.ring = p->ring.p + 1;
-    probe_launch(p, TFK_PROBE_PARTIAL, (unsigned)(s->nsys * p->nblk), (unsigned)p->nseg, a);
-    probe_launch(p, TFK_PROBE_FINAL, (unsigned)s->nsys, 1, a);
+    p->launch(TFK_PROBE_PARTIAL, (unsigned)(s->nsys * p->nblk), (unsigned)p->nseg, 256, &a, sizeof a);
+    p->launch(TFK_PROBE_FINAL, (unsigned)s->nsys, 1, 256, &a, sizeof a);
     ++p->on_device;
     TF_API_END
 }

@@ -1,7 +1,8 @@
 // Host runtime of libtriflow_hip: device recorders (tf_record_*).  A recorder set is one more code object
 // of the solver's model -- the model's translation unit plus the generated record block
 // (codegen.lower_records) -- of which only tfk_record is launched, on the solver's stream, on one of its
-// state slots: one launch per recorder that is due, one row [nsys][ncols] per launch.
+// state slots (tf_observer, tf_solver.h: what the recorders share with the probes): one launch per recorder
+// that is due, one row [nsys][ncols] per launch.
 //
 // The rows of a recorder go into a ring of two halves in device memory.  When a half is full, an event on
 // the solver's stream lets the recorder's copy stream move it into a page-locked buffer of that half
@@ -38,14 +39,8 @@ struct Ring {
 };
 }  // namespace
 
-struct tf_record {
-    tf_solver* solver = nullptr;
-    tfb::Module* module = nullptr;
+struct tf_record : tf_observer {
     tfb::Stream* copy = nullptr;
-    int nhc = 0;
-    int64_t bytes = 0;
-    DevBuf hc, xplane;
-    bool own_x = false;                        // the solver holds no x plane (its model does not read x)
     std::vector<std::unique_ptr<Ring>> rings;
 
     ~tf_record() {
@@ -57,7 +52,6 @@ struct tf_record {
                 tfb::event_destroy(r->copied[h]);
             }
         if (copy) tfb::stream_destroy(copy);
-        if (module) tfb::module_unload(module);
     }
 
     // rows [lo, lo + n) of half h to pinned[h], behind what the solver's stream has queued so far
@@ -97,8 +91,6 @@ int tf_record_create(tf_solver* s, const void* code_object, size_t code_size, in
     require(nrec >= 1 && nrec <= 64, "tf_record_create: 1 ... 64 recorders");
     require(nconst >= 0, "tf_record_create: bad constant count");
     std::unique_ptr<tf_record> p(new tf_record());
-    p->solver = s;
-    p->nhc = nconst;
     const int nsys = s->nsys, N = s->L1.N;
     for (int k = 0; k < nrec; ++k) {
         const int32_t* g = geometry + 6 * k;
@@ -118,11 +110,8 @@ int tf_record_create(tf_solver* s, const void* code_object, size_t code_size, in
         r.half = g[5] / 2;
         r.row = (size_t)nsys * r.ncols;
     }
-    p->module = tfb::module_load(code_object, code_size);
+    p->init(s, code_object, code_size, nconst);
     p->copy = tfb::stream_create();
-    p->hc.alloc((size_t)std::max(nconst, 1) * nsys, p->bytes);
-    p->own_x = !s->spec.uses_x;
-    if (p->own_x) p->xplane.alloc((size_t)s->L1.plane, p->bytes);
     for (auto& rp : p->rings) {
         Ring& r = *rp;
         r.dev.alloc(1 + 2 * (size_t)r.half * r.row, p->bytes);         // (zero-filled: cursor 0)
@@ -141,19 +130,14 @@ void tf_record_destroy(tf_record* p) { delete p; }
 int tf_record_set_consts(tf_record* p, const double* values, int32_t nconst) {
     TF_API_BEGIN
     require(p && (values || nconst == 0), "null argument");
-    require(nconst == p->nhc, "tf_record_set_consts: constant count differs from tf_record_create");
-    const int nsys = p->solver->nsys;
-    std::vector<double> t((size_t)std::max(nconst, 1) * nsys, 0.0);    // [nsys][nconst] -> [nconst][nsys]
-    for (int e = 0; e < nsys; ++e)
-        for (int k = 0; k < nconst; ++k) t[(size_t)k * nsys + e] = values[(size_t)e * nconst + k];
-    tfb::h2d(p->hc.p, t.data(), t.size() * sizeof(double), p->solver->stream);
+    p->set_consts("tf_record", values, nconst);
     TF_API_END
 }
 
 int tf_record_set_x(tf_record* p, const double* x) {
     TF_API_BEGIN
     require(p && x, "null argument");
-    if (p->own_x) p->solver->upload_planes(x, p->xplane.p, 1);
+    p->set_x(x);
     TF_API_END
 }
 
@@ -170,28 +154,14 @@ int tf_record_record(tf_record* p, int32_t which, int32_t slot) {
     }
     TfRecordArgs a;
     std::memset(&a, 0, sizeof a);
-    a.L = s->L1;
-    a.fields = s->st(slot);
-    a.helpers = s->helpers.p;
-    a.parvec = s->parvec.p;
-    a.parsca = s->parsca.p;
-    a.dx = s->dx.p;
-    a.xcoord = p->own_x ? p->xplane.p : s->xcoord.p;
-    a.hc = p->hc.p;
+    static_cast<TfNodeArgs&>(a) = p->node_args(slot);
     a.which = r.expr;
     a.pool = r.pool; a.start = r.start; a.stop = r.stop; a.step = r.step; a.ncols = r.ncols;
     a.split = r.split; a.part = r.part; a.nblk = r.nblk;
     a.capacity = 2 * r.half;
     a.cursor = (int*)r.dev.p;
     a.ring = r.dev.p + 1;
-    const unsigned gx = (unsigned)(s->nsys * r.nblk);
-    if ((s->timing >> TFK_RECORD) & 1ull) {            // (timed like the solver's own launches: tf_timing_get)
-        tf_solver::Stamp st{TFK_RECORD, s->get_event(), s->get_event()};
-        tfb::launch_timed(p->module, TFK_RECORD, gx, 1, TF_REC_BLOCK, &a, sizeof(a), s->stream, st.a, st.b);
-        s->stamps.push_back(st);
-    } else {
-        tfb::launch(p->module, TFK_RECORD, gx, 1, TF_REC_BLOCK, &a, sizeof(a), s->stream);
-    }
+    p->launch(TFK_RECORD, (unsigned)(s->nsys * r.nblk), 1, TF_REC_BLOCK, &a, sizeof a);
     ++r.head;
     if (r.head % r.half == 0) {                        // half h is full: its copy, while the other half fills
         p->take(r, h);                                 // (rows of this half's last round still in pinned[h])

@@ -8,6 +8,8 @@
 //   tf_rt_io.cpp           inputs and outputs: states, parameters, hooks, F / J, tf_factor / tf_solve / tf_matvec
 //   tf_rt_steps.cpp        the time-step drivers Theta / Rosenbrock-Wanner / BDF-2 / step doubling
 //   tf_rt_diag.cpp         counters, monitors, stamps, timing, tf_sync
+//   tf_rt_probe.cpp        device probes (tf_probe_*)   } observers of a resident state slot: tf_observer, at the
+//   tf_rt_record.cpp       device recorders (tf_record_*) } end of this file, is what they share
 #pragma once
 #include "../../include/triflow_hip.h"
 #include "tf_args.h"
@@ -575,4 +577,67 @@ struct tf_solver {
     bool monitored = false;
     // have_flag / have_worst: values that already came back with another download of this call
     void check_status(const int* have_flag = nullptr, const double* have_worst = nullptr);
+};
+
+// What the device observers (tf_probe, tf_record) share.  An observer is one more code object of the solver's
+// model -- the model's translation unit plus a generated block of expressions -- of which only the
+// observer's own kernels are launched, on the solver's stream, on one of its state slots.  Here: the inputs
+// of the node core (TfNodeArgs; csrc/tf_node.h) and the launch.  Rings and copies are the observer's own.
+struct tf_observer {
+    tf_solver* solver = nullptr;
+    tfb::Module* module = nullptr;
+    int nhc = 0;                               // host constants of the expressions
+    int64_t bytes = 0;
+    DevBuf hc, xplane;
+    bool own_x = false;                        // the solver holds no x plane (its model does not read x)
+    ~tf_observer() { if (module) tfb::module_unload(module); }
+
+    void init(tf_solver* s, const void* code_object, size_t code_size, int nconst) {
+        solver = s;
+        nhc = nconst;
+        module = tfb::module_load(code_object, code_size);
+        hc.alloc((size_t)std::max(nconst, 1) * s->nsys, bytes);
+        // x of the nodes (argmax / argmin, expressions that read x): the solver's plane when its model
+        // reads x (bound with the other inputs, tf_set_x), else a plane of the observer's own (set_x)
+        own_x = !s->spec.uses_x;
+        if (own_x) xplane.alloc((size_t)s->L1.plane, bytes);
+    }
+    // values [nsys][nconst]; api: the entry points' prefix ("tf_probe": the message names the caller's)
+    void set_consts(const char* api, const double* values, int nconst) {
+        if (nconst != nhc)
+            throw std::invalid_argument(std::string(api) + "_set_consts: constant count differs from " + api + "_create");
+        const int nsys = solver->nsys;
+        std::vector<double> t((size_t)std::max(nconst, 1) * nsys, 0.0);    // [nsys][nconst] -> [nconst][nsys]
+        for (int e = 0; e < nsys; ++e)
+            for (int k = 0; k < nconst; ++k) t[(size_t)k * nsys + e] = values[(size_t)e * nconst + k];
+        tfb::h2d(hc.p, t.data(), t.size() * sizeof(double), solver->stream);
+    }
+    void set_x(const double* x) {
+        if (own_x) solver->upload_planes(x, xplane.p, 1);
+    }
+    TfNodeArgs node_args(int slot) {
+        tf_solver* s = solver;
+        TfNodeArgs c;
+        std::memset(&c, 0, sizeof c);
+        c.L = s->L1;
+        c.fields = s->st(slot);
+        c.helpers = s->helpers.p;
+        c.parvec = s->parvec.p;
+        c.parsca = s->parsca.p;
+        c.dx = s->dx.p;
+        c.xcoord = own_x ? xplane.p : s->xcoord.p;
+        c.hc = hc.p;
+        return c;
+    }
+    // (timed like the solver's own launches: tf_timing_get)
+    void launch(int kernel, unsigned gx, unsigned gy, unsigned block, const void* args, size_t sz) {
+        tf_solver* s = solver;
+        if ((s->timing >> kernel) & 1ull) {
+            tf_solver::Stamp st{kernel, s->get_event(), s->get_event()};
+            tfb::launch_timed(module, kernel, gx, gy, block, args, sz, s->stream, st.a, st.b);
+            s->stamps.push_back(st);
+        } else {
+            tfb::launch(module, kernel, gx, gy, block, args, sz, s->stream);
+        }
+    }
 };

@@ -13,8 +13,7 @@ table from rank 0 (``broadcast_table``).
 
 import numpy as np
 
-from .probes import ProbeSet
-from .recorders import RecorderSet
+from .observers import Observed
 from .tableaux import TABLEAUX
 
 __all__ = ["Ensemble", "shard_members", "broadcast_table"]
@@ -38,7 +37,7 @@ def broadcast_table(table, src=0):
     return t.cpu().numpy()
 
 
-class Ensemble:
+class Ensemble(Observed):
     """``nsys`` members of the same model on one GPU, stepped together.
 
     ``fields``: dict name -> array ``[nsys][N]`` (dependent variables and help
@@ -127,61 +126,15 @@ class Ensemble:
         self.t += dt
         self._nsteps += 1
         if self._probes is not None:
-            self._record_probes()
+            self._record_on(self._probes)
         if self._recorders is not None:
             self._record_on(self._recorders)
 
-    # ---- device probes (probes.py) ----------------------------------------------------
-    def add_probe(self, name, expression, reduce="sum"):
-        """Record ``reduce`` of ``expression`` over the nodes of every member, now and after every
-        ``step``; ``probes[name] = (t, values[rows, nsys])``.  Values of this rank's members only."""
-        if self._probes is None:
-            self._probes = ProbeSet(self.model)
-        self._probes.add(name, expression, reduce)
-        try:
-            self._record_probes()
-        except Exception:
-            # (no code object / no tf_probe for the new set: the probe is not kept, the others go on)
-            self._probes.remove(name)
-            raise
-
-    def remove_probe(self, name):
-        if self._probes is None:
-            raise KeyError(name)
-        self._probes.remove(name)
-
-    @property
-    def probes(self):
-        return self._probes.series() if self._probes is not None else {}
-
-    def _record_probes(self):
-        self._record_on(self._probes)
+    # ---- device probes and recorders (observers.Observed) ---------------------------------
+    _n_nodes = property(lambda self: self.N)
 
     def _record_on(self, series_set):
         series_set.record(self.solver, self.cur, self.t, self._nsteps, self._x, self._member_pars)
-
-    # ---- device recorders (recorders.py) ----------------------------------------------
-    def add_recorder(self, name, expression, every=1, nodes=slice(None), pool="sample", capacity=None):
-        """Record ``expression`` at the columns ``nodes`` of every member (``Simulation.add_recorder``),
-        now and after every ``every``-th ``step``; ``recorders[name] = (t, x, values[rows, nsys, ncols])``,
-        ``x [nsys, ncols]`` when the members have grids of their own.  This rank's members only."""
-        if self._recorders is None:
-            self._recorders = RecorderSet(self.model, self.N)
-        self._recorders.add(name, expression, every, nodes, pool, capacity)
-        try:
-            self._record_on(self._recorders)
-        except Exception:
-            self._recorders.remove(name)
-            raise
-
-    def remove_recorder(self, name):
-        if self._recorders is None:
-            raise KeyError(name)
-        self._recorders.remove(name)
-
-    @property
-    def recorders(self):
-        return self._recorders.series() if self._recorders is not None else {}
 
     def restart(self):
         """Back to the initial state and t = 0 (parameters, hook and factorisation plan stay; a

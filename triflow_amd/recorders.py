@@ -1,12 +1,13 @@
 """Device recorders: decimated space-time series of model expressions, computed where the state lives.
 
 A recorder is a named expression in the model's own string language (what a probe accepts:
-``probes.discretise``), a window of nodes ``nodes = slice(start, stop, step)``, a pool over the nodes
+``observers.discretise``), a window of nodes ``nodes = slice(start, stop, step)``, a pool over the nodes
 of each bin of ``step`` nodes -- ``"sample"`` (the bin's first node), ``"max"``, ``"min"`` (NaN as
 NumPy has it), ``"mean"`` (a sum in a fixed order over the bin's node count) -- and a stride in steps
 ``every``.  Column ``j`` covers nodes ``start + j*step ... min(start + (j+1)*step, stop) - 1`` and
 ``x[j]`` is the coordinate of the first of them.  The expressions are lowered by
-``codegen.lower_records`` and compiled into one more code object of the model; ``tfk_record``
+``codegen.lower_records`` and compiled into one more code object of the model (``observers.py``: what the recorders share
+with the probes); ``tfk_record``
 (``csrc/tf_record.h``) reads a resident state slot and writes one row per record into the recorder's
 ring in device memory, which comes to the host half by half on a stream of its own (``tf_record_*``).
 A picture of a million nodes leaves the GPU as some KB per recorded row.
@@ -18,7 +19,7 @@ import numpy as np
 
 from . import codegen
 from .codegen import RECORD_POOLS
-from .probes import discretise
+from .observers import ObserverSet, _Bound, discretise  # noqa: F401  (_Bound: the tests build one)
 
 __all__ = ["RecorderSet", "RECORD_POOLS", "DEFAULT_RING_BYTES", "MAX_RING_ROWS", "MAX_RECORDERS"]
 
@@ -55,14 +56,7 @@ class _Recorder:
         return max(2, min(DEFAULT_RING_BYTES // row, MAX_RING_ROWS) & ~1)
 
 
-class _Bound:
-    """One ``tf_record`` (the record kernel on one solver) and what was last uploaded to it."""
-
-    def __init__(self, handle, spec):
-        self.handle, self.spec, self.key = handle, spec, None
-
-
-class RecorderSet:
+class RecorderSet(ObserverSet):
     """The recorders of one Simulation or Ensemble (``N`` nodes per system) and their series.
 
     Rows are recorded on the device (``record``) and fetched when the series are read (``series``):
@@ -70,12 +64,13 @@ class RecorderSet:
     sweep segment of those solvers.  ``capacity``: rows of every recorder's device ring (default:
     ``DEFAULT_RING_BYTES`` worth of rows)."""
 
+    kind = "record"
+
     def __init__(self, model, N, capacity=None):
-        self.model, self.N = model, int(N)
+        super().__init__(model)
+        self.N = int(N)
         self.capacity = capacity
         self._recs = []
-        self._bound = {}             # id(solver) -> _Bound
-        self._blocks = {}            # parvec mask -> (record block, spec)
 
     # ---- the set ---------------------------------------------------------------------
     @property
@@ -126,16 +121,6 @@ class RecorderSet:
         self._recs = [r for r in self._recs if r.name != name]
         self._reset()
 
-    def _reset(self):
-        for b in self._bound.values():
-            b.handle.close()
-        self._bound.clear()
-        self._blocks.clear()
-
-    def close(self):
-        self._flush()
-        self._reset()
-
     # ---- device side -----------------------------------------------------------------
     def expressions(self):
         """The distinct discretised expressions of the set, in the order they were added: recorders
@@ -147,31 +132,20 @@ class RecorderSet:
                 out.append(r.disc)
         return out
 
-    def _lowered(self, mask):
-        if mask not in self._blocks:
-            self._blocks[mask] = codegen.lower_records(self.model, self.expressions(), parvec_mask=mask)
-        return self._blocks[mask]
+    def _lower(self, mask):
+        return codegen.lower_records(self.model, self.expressions(), parvec_mask=mask)
 
     def _bind(self, solver):
-        b = self._bound.get(id(solver))
-        if b is not None and b.handle.solver is solver:
-            return b
-        from . import compilers
-        from ._capi import DeviceRecord
         if solver.N != self.N:
             raise ValueError("the recorders were laid out for %d nodes, the solver has %d" % (self.N, solver.N))
-        spec = solver.model.spec
+        return super()._bind(solver)
+
+    def _make_handle(self, solver, code, spec):
+        from ._capi import DeviceRecord
         exprs = self.expressions()
         geometry = [(exprs.index(r.disc), RECORD_POOLS.index(r.pool), r.start, r.stop, r.step, r.rows_of_ring(solver.nsys))
                     for r in self._recs]
-        block, rspec = self._lowered(spec["parvec_mask"])
-        hsaco = compilers.build_record_code_object(self.model, block, spec["parvec_mask"], spec["seg"],
-                                                   spec["sweep_block"])
-        with open(hsaco, "rb") as f:
-            code = f.read()
-        handle = DeviceRecord(solver, code, geometry, len(rspec["host_consts"]))
-        b = self._bound[id(solver)] = _Bound(handle, rspec)
-        return b
+        return DeviceRecord(solver, code, geometry, len(spec["host_consts"]))
 
     def record(self, solver, slot, t, key, x, member_pars):
         """Queue a row of every recorder that is due: state ``slot`` of ``solver`` (a ``DeviceSolver``).
@@ -183,19 +157,8 @@ class RecorderSet:
                if r.last != key and (r.origin is None or (key - r.origin) % r.every == 0)]
         if not due:
             return
-        b = self._bind(solver)
         x = np.asarray(x, dtype=float)
-        bkey = (x.shape, float(x.flat[0]), float(x.flat[-1]),
-                tuple(tuple(float(np.ravel(v)[0]) for v in pars) for pars in member_pars))
-        if bkey != b.key:
-            x2 = np.broadcast_to(x, (solver.nsys, solver.N))
-            if not solver.model.spec["uses_x"]:          # (else the kernel reads the solver's own x plane)
-                b.handle.set_x(x2)
-            if b.spec["host_consts"]:
-                dxs = (x2[:, -1] - x2[:, 0]) / (solver.N - 1)
-                b.handle.set_consts(np.array([codegen.eval_host_constants(b.spec, dxs[e], member_pars[e])
-                                              for e in range(solver.nsys)]))
-            b.key = bkey
+        b = self._bind_inputs(solver, x, member_pars)
         for k in due:
             r = self._recs[k]
             b.handle.record(k, slot)

@@ -36,8 +36,7 @@ from numpy import isclose
 
 from . import schemes
 from .device import DirichletHook, null_hook, stepper_for
-from .probes import ProbeSet
-from .recorders import RecorderSet
+from .observers import Observed
 
 __all__ = ["Simulation", "PostProcess", "Stream", "Timer"]
 
@@ -77,7 +76,7 @@ def _accepted_kwargs(kwargs, function):
     return {k: v for k, v in kwargs.items() if k in names}
 
 
-class Simulation:
+class Simulation(Observed):
     def __init__(self, model, fields, parameters, dt, t=0, tmax=None, id=None,
                  hook=null_hook, scheme=schemes.RODASPR, time_stepping=True, **kwargs):
         kwargs["time_stepping"] = time_stepping
@@ -138,7 +137,7 @@ class Simulation:
                 self.i += 1
                 self.t, self.fields, self.parameters = t, fields, pars
                 if self._probes is not None:
-                    self._record_probes()
+                    self._record_on(self._probes)
                 if self._recorders is not None:
                     self._record_on(self._recorders)
                 for pprocess in self.post_processes:
@@ -232,33 +231,12 @@ class Simulation:
     def remove_post_process(self, name):
         self._pprocesses = [p for p in self._pprocesses if p.name != name]
 
-    # ---- device probes (probes.py) ----------------------------------------------------
-    def add_probe(self, name, expression, reduce="sum"):
-        """Record ``reduce`` of the model expression ``expression`` over the nodes after every step,
-        on the GPU (``probes.py``): the t0 row now, then one row where the post-processes run.  The
-        series is ``probes[name] = (t, values)``; the fields are never brought to the host for it."""
-        if self._probes is None:
-            self._probes = ProbeSet(self.model)
-        self._probes.add(name, expression, reduce)
-        try:
-            self._record_probes()
-        except Exception:
-            # (no code object / no tf_probe for the new set: the probe is not kept, the others go on)
-            self._probes.remove(name)
-            raise
-
-    def remove_probe(self, name):
-        if self._probes is None:
-            raise KeyError(name)
-        self._probes.remove(name)
+    # ---- device probes and recorders (observers.Observed) ---------------------------------
+    _per_system = False
 
     @property
-    def probes(self):
-        """name -> (t, values): float64 arrays, one entry per recorded state."""
-        return self._probes.series(per_system=False) if self._probes is not None else {}
-
-    def _record_probes(self):
-        self._record_on(self._probes)
+    def _n_nodes(self):
+        return np.asarray(self.fields["x"]).size
 
     def _record_on(self, series_set):
         # the prologue of the device schemes (schemes._device_step): a state that is not resident is
@@ -269,31 +247,6 @@ class Simulation:
         slot = stepper.acquire(fields)
         series_set.record(stepper.solver, slot, self.t, self.i, np.asarray(fields["x"]),
                           [[pars[k] for k in stepper.compiled.pars]])
-
-    # ---- device recorders (recorders.py) ----------------------------------------------
-    def add_recorder(self, name, expression, every=1, nodes=slice(None), pool="sample", capacity=None):
-        """Record the model expression ``expression`` on the GPU at the columns ``nodes`` (a slice; a
-        column is the ``pool`` -- "sample", "max", "min", "mean" -- of a bin of ``nodes.step`` nodes):
-        a row now, then after every ``every``-th step, where the post-processes run.  The series is
-        ``recorders[name] = (t, x, values[rows, ncols])``; the fields never come to the host for it."""
-        if self._recorders is None:
-            self._recorders = RecorderSet(self.model, np.asarray(self.fields["x"]).size)
-        self._recorders.add(name, expression, every, nodes, pool, capacity)
-        try:
-            self._record_on(self._recorders)
-        except Exception:
-            self._recorders.remove(name)       # (not kept, as a probe that cannot run: the others go on)
-            raise
-
-    def remove_recorder(self, name):
-        if self._recorders is None:
-            raise KeyError(name)
-        self._recorders.remove(name)
-
-    @property
-    def recorders(self):
-        """name -> (t, x, values): float64 arrays, one row of values per recorded state."""
-        return self._recorders.series(per_system=False) if self._recorders is not None else {}
 
     def save_recorder(self, name, path):
         """The series of recorder ``name`` as a container directory that ``retrieve_container`` reads."""

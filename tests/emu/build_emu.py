@@ -66,12 +66,12 @@ def build(model, parvec_mask=0, opt="-O1"):
 class EmuBackend:
     """Drop-in for triflow_amd.compilers.HipBackend in CPU tests."""
 
-    def __init__(self):
-        self._libs = {}
+    def __init__(self, opt="-O1"):
+        self._libs, self._opt = {}, opt
 
     def load(self, model, parvec_mask):
         from triflow_amd._capi import DeviceModel, Library
-        so, spec = build(model, parvec_mask)
+        so, spec = build(model, parvec_mask, self._opt)
         if so not in self._libs:
             self._libs[so] = Library(so)
         return DeviceModel(self._libs[so], spec, b"")

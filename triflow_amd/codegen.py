@@ -349,6 +349,15 @@ def _lower_node_expressions(model, exprs, parvec_mask):
     pars = list(model._pars)
     mp = max((model._window_range - 1) // 2, 1)
     names, decls, uniform = _stencil_names(fields, pars, mp, parvec_mask)
+    import sympy
+    for e in exprs:
+        # In F and J, Heaviside is identically one (the reference's module dictionary: it only ever
+        # stands there as the derivative of Max / Min).  An observer is not differentiated: a Heaviside
+        # in it is the user's own, and a step function that is one everywhere is not what they wrote.
+        if sympy.sympify(e).has(sympy.Heaviside):
+            raise UnsupportedExpression("function 'Heaviside' is not supported in a probe or recorder: the HIP "
+                                        "compiler takes it as identically one, as the reference does in J; "
+                                        "write the step with Max / Min / sign")
     nodes = _printed_expressions(model._symbolic_args, list(exprs))
     first = _CEmitter(names, uniform)               # pass 1: count divisor reuse
     for n in nodes:

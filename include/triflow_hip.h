@@ -224,6 +224,12 @@ int tf_monitor_error(tf_solver*, double* worst);
  * checks that waited for the device, and factorisations that were redone on longer chunks because
  * the first attempt lost accuracy */
 int tf_solver_counters(tf_solver*, int64_t* factorisations, int64_t* checks, int64_t* replans);
+/* F+J sweeps since the solver was created.  The planes of the value table that hold node-independent
+ * entries (spec["j_uniform"]: functions of dx, the scalar parameters and constants) are written by the
+ * first sweep after tf_set_param_scalar / tf_set_param_vector / tf_set_dx and left alone by the following
+ * ones (`lean`), their values being the same; the table tf_get_J reads is complete at all times.
+ * `full` counts the sweeps that wrote every plane (all of them with TRIFLOW_J_UNIFORM_ONCE=0). */
+int tf_jacobian_sweeps(tf_solver*, int64_t* full, int64_t* lean);
 /* the workgroup size a kernel of the model's code object was built for (tfk_l1_factor*: 128 when
  * the factorisation walks are split over two wavefronts, tf_args.h TF_L1_SPLIT_MODEL) */
 int tf_solver_kernel_block(tf_solver*, int32_t kernel, int32_t* block);

@@ -89,6 +89,7 @@ SIGNATURES = {
     "tf_backward_error": (C.c_int, [C.c_void_p, c_double_p, c_int32_p]),
     "tf_monitor_error": (C.c_int, [C.c_void_p, c_double_p]),
     "tf_solver_counters": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p, c_int64_p]),
+    "tf_jacobian_sweeps": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p]),
     "tf_sync": (C.c_int, [C.c_void_p]),
     "tf_timing_enable": (C.c_int, [C.c_void_p, C.c_int64]),
     "tf_timing_reset": (C.c_int, [C.c_void_p]),
@@ -448,6 +449,13 @@ class DeviceSolver:
         f, c, r = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         self.lib.call("tf_solver_counters", self.handle, C.byref(f), C.byref(c), C.byref(r))
         return dict(factorisations=f.value, checks=c.value, replans=r.value)
+
+    def jacobian_sweeps(self):
+        """dict(full, lean): F+J sweeps that wrote every plane of the value table / that left the
+        node-independent planes alone (written once per upload of a parameter or dx)."""
+        f, n = C.c_int64(0), C.c_int64(0)
+        self.lib.call("tf_jacobian_sweeps", self.handle, C.byref(f), C.byref(n))
+        return dict(full=f.value, lean=n.value)
 
     def kernel_block(self, name):
         """Workgroup size the kernel ``name`` of the model's code object was built for."""

@@ -57,6 +57,10 @@ struct TfSweepArgs {               // F / F+J stencil sweep, J @ v, A-row build
     double* bdf_prev_out;
     double bdf_c0, bdf_c1;
     int bdf_two_step;
+    // F+J sweeps, 1: the node-independent planes of Jv (tf_j_uniform) already hold the values of the
+    // current scalar parameters and dx (an earlier sweep wrote them); this launch leaves them alone.
+    // (In the padding behind bdf_two_step: no other argument moves.)
+    int ju_valid;
     // tfk_sweep_f_stage_rhs: the right-hand side of Rosenbrock stage i in the pass that evaluates
     // its F:  rhs = cF*(fscale*F(U + sum_j kc_j k_j)) + cA*(J @ (sum_j gc_j k_j)), the operations of
     // tfk_sweep_f_stage followed by tfk_spmv's stage form, in their order (schemes.py:152-160).

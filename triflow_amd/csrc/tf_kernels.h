@@ -170,9 +170,11 @@ struct TfJUniform {
 // NTERMS > 0 (stage forms): the number of stage vectors k_j is a compile-time constant, so that the
 // loads of a node's k_j are all issued before the first is used (with the run-time loop they went one
 // after the other: the stage pass of RODASPR's later stages ran at 2.8 TB/s, profiles/r04_ab_runs.txt)
-template <bool WITH_J, bool STAGE = false, bool THETA = false, bool BDF = false, bool STAGE_RHS = false,
-          int SEG = TF_SEG, int NTERMS = 0>
-TF_DEVICE void tfk_sweep_body(const TfSweepArgs& a, int pg, int seg) {
+// SKIP_JU (TfSweepArgs::ju_valid, the same for the whole launch): the node-independent planes of the
+// value table hold what this sweep would write -- they are neither evaluated nor stored; the other
+// entries, the proportional ones (tf_j_alias) included, are written as ever.
+template <bool WITH_J, bool STAGE, bool THETA, bool BDF, bool STAGE_RHS, int SEG, int NTERMS, bool SKIP_JU>
+TF_DEVICE void tfk_sweep_impl(const TfSweepArgs& a, int pg, int seg) {
     const TfLayout& L = a.L;
     if (pg >= L.Ptot) return;
     const int e = pg / L.P, p = pg - e * L.P;
@@ -220,7 +222,7 @@ TF_DEVICE void tfk_sweep_body(const TfSweepArgs& a, int pg, int seg) {
     double w[TF_NF][TF_W];
     double wv[STAGE_RHS ? TF_NVAR : 1][TF_W];
     TfJUniform ju;
-    if (STAGE_RHS) ju.init(a.parsca, a.dx, L.nsys, e);
+    if (STAGE_RHS || (THETA && SKIP_JU)) ju.init(a.parsca, a.dx, L.nsys, e);
 #pragma unroll
     for (int f = 0; f < TF_NF; ++f)
 #pragma unroll
@@ -279,10 +281,11 @@ TF_DEVICE void tfk_sweep_body(const TfSweepArgs& a, int pg, int seg) {
             }
             if (WITH_J) {
                 double Jo[TF_NNZ > 0 ? TF_NNZ : 1];
-                tf_eval_J(w, par, dx, xc, Jo);
+                tf_eval_J(w, par, dx, xc, Jo);      // (SKIP_JU: nothing reads the uniform entries of this call)
 #pragma unroll
                 for (int k = 0; k < TF_NNZ; ++k)
-                    TF_STORE_STREAM((double*)((char*)(a.Jv + (int64_t)k * L.plane) + off), Jo[k]);
+                    if (!(SKIP_JU && TF_JU(k)))
+                        TF_STORE_STREAM((double*)((char*)(a.Jv + (int64_t)k * L.plane) + off), Jo[k]);
                 if (BDF) {
                     // TF_VEC_BDF2_RHS and the copy of U into the history, per node
 #pragma unroll
@@ -302,7 +305,8 @@ TF_DEVICE void tfk_sweep_body(const TfSweepArgs& a, int pg, int seg) {
                     for (int v = 0; v < TF_NVAR; ++v) acc[v] = 0.0;
 #pragma unroll
                     for (int k = 0; k < TF_NNZ; ++k) {
-                        const double jv = a.theta * Jo[k];
+                        // (the uniform entries from the scalars, as in the stage pass: same expressions, same bits)
+                        const double jv = a.theta * ((SKIP_JU && TF_JU(k)) ? ju.v[k] : Jo[k]);
                         acc[tf_pat_eq[k]] = acc[tf_pat_eq[k]] + jv * w[tf_pat_var[k]][tf_pat_off[k] + TF_MP];
                     }
 #pragma unroll
@@ -313,6 +317,16 @@ TF_DEVICE void tfk_sweep_body(const TfSweepArgs& a, int pg, int seg) {
             }
         }
     }
+}
+
+// One wavefront-uniform branch per launch picks the form (a scalar compare of a kernel argument).
+template <bool WITH_J, bool STAGE = false, bool THETA = false, bool BDF = false, bool STAGE_RHS = false,
+          int SEG = TF_SEG, int NTERMS = 0>
+TF_DEVICE void tfk_sweep_body(const TfSweepArgs& a, int pg, int seg) {
+    if constexpr (WITH_J) {
+        if (a.ju_valid) { tfk_sweep_impl<WITH_J, STAGE, THETA, BDF, STAGE_RHS, SEG, NTERMS, true>(a, pg, seg); return; }
+    }
+    tfk_sweep_impl<WITH_J, STAGE, THETA, BDF, STAGE_RHS, SEG, NTERMS, false>(a, pg, seg);
 }
 
 // ===========================================================================

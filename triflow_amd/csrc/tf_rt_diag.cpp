@@ -45,6 +45,16 @@ int tf_solver_counters(tf_solver* s, int64_t* factorisations, int64_t* checks, i
     TF_API_END
 }
 
+// F+J sweeps of this solver so far: those that wrote every plane of the value table, and those that left
+// the node-independent planes alone (tf_solver::ju_once)
+int tf_jacobian_sweeps(tf_solver* s, int64_t* full, int64_t* lean) {
+    TF_API_BEGIN
+    require(s, "null solver");
+    if (full) *full = s->n_sweeps_full;
+    if (lean) *lean = s->n_sweeps_lean;
+    TF_API_END
+}
+
 int tf_solver_kernel_block(tf_solver* s, int32_t kernel, int32_t* block) {
     TF_API_BEGIN
     require(s && block, "null argument");

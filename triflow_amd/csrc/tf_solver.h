@@ -433,6 +433,24 @@ struct tf_solver {
     // which set of factor buffers a step with this c will run on, and whether it reuses what is there
     // (both go into the key of a captured step)
     std::string slot_key(double c) const;
+    // Node-independent planes of the value table Jv (tf_j_uniform: entries of dx, the scalar parameters
+    // and constants only).  Nothing on the device loads them (TfJUniform), and their values change only
+    // when a parameter or dx is uploaded, which par_ver counts: the first F+J sweep after such an upload
+    // writes the whole table, the following ones leave those planes alone (TfSweepArgs::ju_valid), so the
+    // table in memory is complete at all times.  Whoever else writes Jv calls ju_invalidate().  The flag
+    // is a kernel argument, hence part of the key of a captured step (slot_key).
+    bool ju_once = true;           // (TRIFLOW_J_UNIFORM_ONCE=0: every sweep writes every plane; A/B runs, tests)
+    bool ju_written = false;
+    uint64_t ju_ver = 0;
+    int64_t n_sweeps_full = 0, n_sweeps_lean = 0;     // F+J sweeps that wrote every plane / skipped the uniform ones
+    bool ju_current() const { return ju_once && ju_written && ju_ver == par_ver; }
+    void ju_invalidate() { ju_written = false; }
+    // the flag of the F+J sweep about to be launched (captured or replayed: the same bookkeeping)
+    int ju_take() {
+        if (ju_current()) { ++n_sweeps_lean; return 1; }
+        ++n_sweeps_full; ju_written = true; ju_ver = par_ver;
+        return 0;
+    }
     bool l1_respike = false;       // level-1 spike response not stored (tf_args.h, TF_RESPIKE_*)
     int l1_twist = -1;             // -1: by the number of chunks; 0 / 1: TRIFLOW_L1_TWIST (tests, A/B runs)
     // level 1 below a cyclic-reduction level with b <= 6 (TF_FUSE_ASM_OK of tf_entry_hip.h): the walks

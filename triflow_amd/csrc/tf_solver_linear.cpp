@@ -302,7 +302,8 @@ void tf_solver::delegate_factor(double c) {
     copy(fb->dx.p, dx.p, (size_t)nsys * sizeof(double));
     ++fb->par_ver;
     if (spec.parvec_mask) transfer_to(fb, parvec.p, fb->parvec.p, spec.npar);
-    if (spec.nnz > 0) transfer_to(fb, Jv.p, fb->Jv.p, spec.nnz);
+    if (spec.nnz > 0) transfer_to(fb, Jv.p, fb->Jv.p, spec.nnz);      // (every plane: the table here is complete)
+    fb->ju_invalidate();                         // (the child's own sweeps, if it ever ran one, start afresh)
     fb->have_jac = true;
     fb->have_factor = false;
     fb->factor(c);

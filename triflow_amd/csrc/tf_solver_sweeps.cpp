@@ -66,6 +66,7 @@ void tf_solver::sweep(const double* fields, bool with_j, int nterms, const doubl
     a.dx = dx.p; a.xcoord = xcoord.p; a.F = Fout ? Fout : F.p; a.Jv = Jv.p; a.with_j = with_j ? 1 : 0;
     unsigned gx = sweep_gx(), gy = cdiv(L1.M, spec.seg);
     if (nterms > 0 && with_j) throw std::logic_error("stage sweep evaluates F only");
+    if (with_j) a.ju_valid = ju_take();
     launch(with_j ? TFK_SWEEP_FJ : (nterms > 0 ? TFK_SWEEP_F_STAGE : TFK_SWEEP_F), gx, gy,
            spec.sweep_block, &a, sizeof(a));
     if (with_j) { have_jac = true; have_factor = false; }
@@ -77,6 +78,7 @@ void tf_solver::sweep_bdf2(const double* fields, bool two_step, double c0, doubl
     a.fscale = 1.0;
     a.L = L1; a.fields = fields; a.helpers = helpers.p; a.parvec = parvec.p; a.parsca = parsca.p;
     a.dx = dx.p; a.xcoord = xcoord.p; a.F = nullptr; a.Jv = Jv.p; a.with_j = 1;
+    a.ju_valid = ju_take();
     a.bdf_rhs = rhs; a.bdf_prev = prev; a.bdf_prev_out = prev_out; a.bdf_c0 = c0; a.bdf_c1 = c1; a.bdf_two_step = two_step ? 1 : 0;
     unsigned gx = sweep_gx(), gy = cdiv(L1.M, spec.seg);
     launch(TFK_SWEEP_FJ_BDF2, gx, gy, spec.sweep_block, &a, sizeof(a));
@@ -89,6 +91,7 @@ void tf_solver::sweep_theta(const double* fields, double dt, double theta, doubl
     a.fscale = 1.0;
     a.L = L1; a.fields = fields; a.helpers = helpers.p; a.parvec = parvec.p; a.parsca = parsca.p;
     a.dx = dx.p; a.xcoord = xcoord.p; a.F = nullptr; a.Jv = Jv.p; a.with_j = 1;
+    a.ju_valid = ju_take();
     a.theta_rhs = rhs; a.theta = theta; a.theta_dt = dt;
     unsigned gx = sweep_gx(), gy = cdiv(L1.M, spec.seg);
     launch(TFK_SWEEP_FJ_THETA, gx, gy, spec.sweep_block, &a, sizeof(a));
@@ -144,7 +147,8 @@ void tf_solver::swap_slots() {
 std::string tf_solver::slot_key(double c) const {
     const bool reuse = reuse_ok(c) || alt_ok(c);
     const int slot = reuse_ok(c) ? slot_id : ((alt_ok(c) || wants_alt(c)) ? slot_id ^ 1 : slot_id);
-    return std::string(reuse ? "|u" : "|f") + (slot ? "1" : "0");
+    // (... and whether the step's F+J sweep leaves the node-independent planes alone: a kernel argument)
+    return std::string(reuse ? "|u" : "|f") + (slot ? "1" : "0") + (ju_current() ? "j" : "J");
 }
 
 bool tf_solver::fuse_asm_ok() const {

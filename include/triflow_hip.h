@@ -296,6 +296,33 @@ int tf_record_fetch(tf_record*, int32_t which, double* out, int64_t max_rows, in
 /* rows of recorder `which` recorded and not fetched yet (no wait) */
 int tf_record_pending(tf_record*, int32_t which, int64_t* rows);
 
+/* ---- device statistics: per-node statistics over time of model expressions on a resident state slot ----
+ * code_object: the model's code object rebuilt with the generated statistic block
+ * (codegen.lower_statistics; built with the solver's parameter layout and sweep segment), of which only
+ * tfk_stat is launched.  geometry[nstat][2]: the expression of the block (statistics may share one; the
+ * expressions are numbered in the order the statistics first use them: 0, then at most one more) and
+ * the kind: 0 mean, 1 var (running mean and sum of squared deviations M2; the variance is M2 / n),
+ * 2 max, 3 min (NaN as numpy has it), 4 argmax, 5 argmin (the extremum and the t of the first sample
+ * that attained it; the first NaN's t wins and stays).  A statistic owns one plane (mean, max, min) or
+ * two (var: mean, M2; argmax, argmin: value, t) of [nsys][N] doubles.  An update is queued on the
+ * solver's stream (no host wait) and folds state `slot` into statistic `which` as sample k (1, 2, ...;
+ * the caller counts: sample 1 overwrites, so starting over costs nothing) taken at time t.  A statistic
+ * set belongs to its solver: destroy it first. */
+typedef struct tf_stat tf_stat;
+int tf_stat_create(tf_solver*, const void* code_object, size_t code_size, int32_t nstat,
+                   const int32_t* geometry, int32_t nconst, tf_stat** out);
+void tf_stat_destroy(tf_stat* stat);
+int tf_stat_set_consts(tf_stat*, const double* values /*[nsys][nconst]*/, int32_t nconst);
+/* coordinates of the nodes (expressions that read x); ignored when the solver's model reads x itself */
+int tf_stat_set_x(tf_stat*, const double* x /*[nsys][N]*/);
+int tf_stat_update(tf_stat*, int32_t which, int32_t slot, int64_t k, double t);
+/* planes of statistic `which` (1 or 2, by its kind): the size of what fetch hands over and load takes */
+int tf_stat_planes_of(tf_stat*, int32_t which, int32_t* planes);
+/* waits, then hands over the planes of statistic `which` in natural order, out[planes][nsys][N] */
+int tf_stat_fetch(tf_stat*, int32_t which, double* out);
+/* the inverse of tf_stat_fetch: in[planes][nsys][N] become the planes of statistic `which` */
+int tf_stat_load(tf_stat*, int32_t which, const double* in);
+
 #ifdef __cplusplus
 }
 #endif

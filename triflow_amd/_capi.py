@@ -114,6 +114,15 @@ SIGNATURES = {
     "tf_record_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "tf_record_fetch": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int64, c_int64_p]),
     "tf_record_pending": (C.c_int, [C.c_void_p, C.c_int32, c_int64_p]),
+    "tf_stat_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, c_int32_p, C.c_int32,
+                                 C.POINTER(C.c_void_p)]),
+    "tf_stat_destroy": (None, [C.c_void_p]),
+    "tf_stat_set_consts": (C.c_int, [C.c_void_p, c_double_p, C.c_int32]),
+    "tf_stat_set_x": (C.c_int, [C.c_void_p, c_double_p]),
+    "tf_stat_update": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_double]),
+    "tf_stat_planes_of": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "tf_stat_fetch": (C.c_int, [C.c_void_p, C.c_int32, c_double_p]),
+    "tf_stat_load": (C.c_int, [C.c_void_p, C.c_int32, c_double_p]),
 }
 
 
@@ -513,7 +522,7 @@ class DeviceSolver:
 
 
 class _DeviceObserver:
-    """What ``tf_probe`` and ``tf_record`` share: a code object of expressions bound to one solver, the
+    """What ``tf_probe``, ``tf_record`` and ``tf_stat`` share: a code object of expressions bound to one solver, the
     x plane and the host constants of the expressions.  ``_prefix``: of the C entry points, ``_noun``:
     what the error message calls the set."""
 
@@ -615,3 +624,35 @@ class DeviceRecord(_DeviceObserver):
     def fetch(self, which):
         """Every row of recorder ``which`` recorded since its last fetch, ``[rows][nsys][ncols]``."""
         return self._fetch(self.ncols[which], int(which))
+
+
+class DeviceStat(_DeviceObserver):
+    """``tf_stat``: the statistic kernel of one statistic set bound to one solver, and the accumulators."""
+
+    _prefix, _noun = "tf_stat", "statistic"
+
+    def __init__(self, solver, code, geometry, nconst):
+        """``geometry``: per statistic ``(expression, kind)``; ``kind``: index into
+        ``statistics.STATISTIC_KINDS``."""
+        g = np.ascontiguousarray(geometry, dtype=np.int32).reshape(-1, 2)
+        self._create(solver, code, nconst, len(g), g.ctypes.data_as(c_int32_p), int(nconst))
+        self.planes = []                         # per statistic, as the library sized them (tf_stat_planes)
+        for k in range(len(g)):
+            n = C.c_int32(0)
+            self._call("planes_of", k, C.byref(n))
+            self.planes.append(n.value)
+
+    def update(self, which, slot, k, t):
+        """Fold state ``slot`` into statistic ``which`` as sample ``k`` (1: the first) taken at ``t``."""
+        self._call("update", int(which), int(slot), int(k), float(t))
+
+    def fetch(self, which):
+        """The accumulators of statistic ``which``, ``[planes][nsys][N]`` (waits for the stream)."""
+        out = np.empty((self.planes[which], self.solver.nsys, self.solver.N))
+        self._call("fetch", int(which), _dptr(out))
+        return out
+
+    def load(self, which, planes):
+        """The inverse of ``fetch``."""
+        a = _f64(planes, (self.planes[which], self.solver.nsys, self.solver.N))
+        self._call("load", int(which), _dptr(a))

@@ -392,11 +392,39 @@ struct TfRecordArgs : TfNodeArgs {
     int* cursor;                   // [0]: next row of the ring (wraps at capacity), [1]: workgroups done with it
     double* ring;                  // [capacity][nsys][ncols]
 };
+
+// Device statistics (tf_stat.h, tf_rt_stat.cpp): per-node statistics over time of model expressions.
+// tfk_stat evaluates expression `which` of the statistic block at every node of a resident state slot and
+// folds the value, sample k (1, 2, ...) taken at time t, into the statistic's accumulator planes.  The
+// planes have the solver's own partition-interleaved layout (TfLayout: node i of chunk p of system e at
+// tf_idx(L, e * P + p, i)), so a thread updates the elements of the nodes it walks and no others.  Grid
+// and walk as tfk_probe_partial: (nsys * nblk, nseg), one thread per segment of TF_PROBE_SEG nodes.
+// Kinds (statistics.STATISTIC_KINDS: same order) and their planes:
+#define TF_STAT_MEAN 0             // [0] running mean m_k = m_{k-1} + (v_k - m_{k-1}) / k
+#define TF_STAT_VAR 1              // [0] running mean, [1] M2_k = M2_{k-1} + (v_k - m_{k-1}) * (v_k - m_k)
+#define TF_STAT_MAX 2              // [0] the extremum, NaN as numpy has it (tf_node_extremum)
+#define TF_STAT_MIN 3
+#define TF_STAT_ARGMAX 4           // [0] the extremum, [1] t of the first sample that attained it (the first
+#define TF_STAT_ARGMIN 5           //     NaN's t wins and stays)
+#define TF_STAT_KINDS 6
+static inline int tf_stat_planes(int kind) {
+    return kind == TF_STAT_VAR || kind == TF_STAT_ARGMAX || kind == TF_STAT_ARGMIN ? 2 : 1;
+}
+struct TfStatArgs : TfNodeArgs {
+    int which;                     // expression of the statistic block (tf_eval_stat's first argument)
+    int kind;                      // TF_STAT_*
+    int nblk;                      // workgroups per system and segment row
+    int nseg;                      // segments of TF_PROBE_SEG nodes per chunk
+    double k;                      // number of this sample, 1 for the first: it is written, nothing is read
+    double t;                      // time of this sample (argmax / argmin)
+    double* acc;                   // [tf_stat_planes(kind)] planes
+};
 // (passed by value to kernels of code objects the host did not compile: the bytes are the contract)
 // (the base comes first and the members follow in their order: the sizes pin the bytes)
 static_assert(sizeof(TfNodeArgs) == 96, "TfNodeArgs changed its layout");
 static_assert(sizeof(TfProbeArgs) == 144, "TfProbeArgs changed its layout");
 static_assert(sizeof(TfRecordArgs) == 152, "TfRecordArgs changed its layout");
+static_assert(sizeof(TfStatArgs) == 136, "TfStatArgs changed its layout");
 
 // Kernel table: index = launch id used by the runtime, name = entry point in
 // the per-model code object (tf_entry_hip.h).  New entries go at the end: the
@@ -424,11 +452,19 @@ enum TfKernel {
     "tfk_probe_partial", "tfk_probe_final" }
 // ... continued: the kernels of the recorders (ids TFK_RECORD ...), a table of their own
 #define TF_KERNEL_NAMES_RECORD { "tfk_record" }
+// ... and the launch ids after TFK_COUNT, with a table of their own as well: the kernel of the statistics.
+// TFK_TOTAL is the number of kernels of a code object: what the runtime sizes and loops by.
+enum TfKernelMore { TFK_STAT = TFK_COUNT, TFK_TOTAL };
+#define TF_KERNEL_NAMES_STAT { "tfk_stat" }
 static inline const char* tf_kernel_entry(int kernel) {
     static const char* const base[] = TF_KERNEL_NAMES;
     static const char* const rec[] = TF_KERNEL_NAMES_RECORD;
+    static const char* const stat[] = TF_KERNEL_NAMES_STAT;
     static_assert(sizeof(base) / sizeof(base[0]) == TFK_RECORD, "TF_KERNEL_NAMES and TfKernel differ");
     static_assert(sizeof(rec) / sizeof(rec[0]) == TFK_COUNT - TFK_RECORD, "TF_KERNEL_NAMES_RECORD and TfKernel differ");
-    if (kernel < 0 || kernel >= TFK_COUNT) return "";
+    static_assert(sizeof(stat) / sizeof(stat[0]) == TFK_TOTAL - TFK_STAT, "TF_KERNEL_NAMES_STAT and TfKernelMore differ");
+    static_assert(TFK_TOTAL <= 64, "the timing mask has one bit per kernel");
+    if (kernel < 0 || kernel >= TFK_TOTAL) return "";
+    if (kernel >= TFK_STAT) return stat[kernel - TFK_STAT];
     return kernel < TFK_RECORD ? base[kernel] : rec[kernel - TFK_RECORD];
 }

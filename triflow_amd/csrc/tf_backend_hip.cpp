@@ -22,7 +22,7 @@ static void check(hipError_t err, const char* what) {
 }
 #define TF_HIP(call) check((call), #call)
 
-struct Module { hipModule_t mod; hipFunction_t fn[TFK_COUNT]; hipModule_t alt = nullptr; };
+struct Module { hipModule_t mod; hipFunction_t fn[TFK_TOTAL]; hipModule_t alt = nullptr; };
 struct Stream { hipStream_t s; };
 struct Event { hipEvent_t e; };
 
@@ -170,7 +170,7 @@ Module* module_load(const void* image, size_t) {
         delete m;
         check(err, "hipModuleLoadData (is the code object built for this GPU, gfx950?)");
     }
-    for (int k = 0; k < TFK_COUNT; ++k) {
+    for (int k = 0; k < TFK_TOTAL; ++k) {
         err = hipModuleGetFunction(&m->fn[k], m->mod, tf_kernel_entry(k));
         if (err != hipSuccess) {
             (void)hipModuleUnload(m->mod);
@@ -190,7 +190,7 @@ Module* module_load(const void* image, size_t) {
             if (fread(&img[0], 1, n, f) == (size_t)n) {
                 hipModule_t am;
                 if (hipModuleLoadData(&am, img.data()) == hipSuccess)
-                    for (int k = 0; k < TFK_COUNT; ++k)
+                    for (int k = 0; k < TFK_TOTAL; ++k)
                         if ((mask >> k) & 1ul) (void)hipModuleGetFunction(&m->fn[k], am, tf_kernel_entry(k));
             }
         }
@@ -202,7 +202,7 @@ void module_add_alternate(Module* m, const void* image, size_t, uint64_t mask) {
     if (!m || !mask) return;
     if (m->alt) throw std::runtime_error("module_add_alternate: one alternate build per model");
     check(hipModuleLoadData(&m->alt, image), "hipModuleLoadData (alternate build)");
-    for (int k = 0; k < TFK_COUNT; ++k)
+    for (int k = 0; k < TFK_TOTAL; ++k)
         if ((mask >> k) & 1ull) {
             if (hipModuleGetFunction(&m->fn[k], m->alt, tf_kernel_entry(k)) != hipSuccess)
                 throw std::runtime_error(std::string("kernel missing from the alternate code object: ") + tf_kernel_entry(k));

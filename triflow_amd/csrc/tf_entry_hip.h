@@ -9,6 +9,7 @@
 #include "tf_cr3_hip.h"
 #include "tf_probe.h"
 #include "tf_record.h"
+#include "tf_stat.h"
 
 #define TF_GID ((int)(blockIdx.x * blockDim.x + threadIdx.x))
 

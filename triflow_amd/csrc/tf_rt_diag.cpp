@@ -58,7 +58,7 @@ int tf_jacobian_sweeps(tf_solver* s, int64_t* full, int64_t* lean) {
 int tf_solver_kernel_block(tf_solver* s, int32_t kernel, int32_t* block) {
     TF_API_BEGIN
     require(s && block, "null argument");
-    require(kernel >= 0 && kernel < TFK_COUNT, "no such kernel");
+    require(kernel >= 0 && kernel < TFK_TOTAL, "no such kernel");
     *block = (int32_t)tfb::kernel_block(s->model->module, kernel);
     TF_API_END
 }
@@ -83,13 +83,13 @@ int tf_timing_reset(tf_solver* s) {
     TF_API_BEGIN
     require(s, "null solver");
     s->collect_timing();
-    for (int k = 0; k < TFK_COUNT; ++k) { s->time_ms[k] = 0; s->time_n[k] = 0; }
+    for (int k = 0; k < TFK_TOTAL; ++k) { s->time_ms[k] = 0; s->time_n[k] = 0; }
     TF_API_END
 }
 int tf_timing_get(tf_solver* s, int32_t kernel, double* total_ms, int64_t* launches) {
     TF_API_BEGIN
     require(s, "null solver");
-    require(kernel >= 0 && kernel < TFK_COUNT, "tf_timing_get: kernel index");
+    require(kernel >= 0 && kernel < TFK_TOTAL, "tf_timing_get: kernel index");
     s->collect_timing();
     if (total_ms) *total_ms = s->time_ms[kernel];
     if (launches) *launches = s->time_n[kernel];

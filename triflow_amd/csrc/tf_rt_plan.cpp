@@ -31,7 +31,7 @@ int tf_set_device(int32_t ordinal) {
     TF_API_END
 }
 
-int tf_kernel_count(void) { return TFK_COUNT; }
+int tf_kernel_count(void) { return TFK_TOTAL; }
 const char* tf_kernel_name(int32_t kernel) {
     return tf_kernel_entry(kernel);
 }

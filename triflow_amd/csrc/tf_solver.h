@@ -10,6 +10,7 @@
 //   tf_rt_diag.cpp         counters, monitors, stamps, timing, tf_sync
 //   tf_rt_probe.cpp        device probes (tf_probe_*)   } observers of a resident state slot: tf_observer, at the
 //   tf_rt_record.cpp       device recorders (tf_record_*) } end of this file, is what they share
+//   tf_rt_stat.cpp         device statistics (tf_stat_*)  }
 #pragma once
 #include "../../include/triflow_hip.h"
 #include "tf_args.h"
@@ -321,8 +322,8 @@ struct tf_solver {
     struct Stamp { int kernel; tfb::Event *a, *b; };
     std::vector<Stamp> stamps;
     std::vector<tfb::Event*> event_pool;
-    double time_ms[TFK_COUNT] = {0};
-    int64_t time_n[TFK_COUNT] = {0};
+    double time_ms[TFK_TOTAL] = {0};
+    int64_t time_n[TFK_TOTAL] = {0};
 
     ~tf_solver() {
         for (auto& st : stamps) { tfb::event_destroy(st.a); tfb::event_destroy(st.b); }
@@ -597,7 +598,7 @@ struct tf_solver {
     void check_status(const int* have_flag = nullptr, const double* have_worst = nullptr);
 };
 
-// What the device observers (tf_probe, tf_record) share.  An observer is one more code object of the solver's
+// What the device observers (tf_probe, tf_record, tf_stat) share.  An observer is one more code object of the solver's
 // model -- the model's translation unit plus a generated block of expressions -- of which only the
 // observer's own kernels are launched, on the solver's stream, on one of its state slots.  Here: the inputs
 // of the node core (TfNodeArgs; csrc/tf_node.h) and the launch.  Rings and copies are the observer's own.

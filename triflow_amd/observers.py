@@ -1,4 +1,5 @@
-"""Device observers: what the probes (``probes.py``) and the recorders (``recorders.py``) share.
+"""Device observers: what the probes (``probes.py``), the recorders (``recorders.py``) and the statistics
+(``statistics.py``) share.
 
 An observer evaluates expressions in the model's own string language at the nodes of a resident state
 slot and writes one row per record into a ring in device memory.  Both kinds go through the same node
@@ -62,7 +63,7 @@ class _Bound:
 class ObserverSet:
     """The code objects and handles of a set of observers: one handle per solver the set has run on, one
     code object per parameter layout / sweep segment of those solvers.  Subclasses: ``kind`` ("probe" /
-    "record": ``compilers.build_observer_code_object``), ``_lower(mask) -> (block, spec)``,
+    "record" / "stat": ``compilers.build_observer_code_object``), ``_lower(mask) -> (block, spec)``,
     ``_make_handle(solver, code, spec)`` and ``_flush()`` (every row still on the device to the series)."""
 
     kind = None
@@ -123,10 +124,10 @@ class ObserverSet:
 class Observed:
     """``add_probe`` / ``add_recorder`` ... of a front end (``Simulation``, ``Ensemble``).  The front end
     has ``model``, says how a set records its current state (``_record_on(series_set)``: also called after
-    every step for ``_probes`` and ``_recorders`` that are not None), how many nodes a system has
+    every step for ``_probes``, ``_recorders`` and ``_statistics`` that are not None), how many nodes a system has
     (``_n_nodes``) and whether its series keep the axis of the systems (``_per_system``)."""
 
-    _probes = _recorders = None
+    _probes = _recorders = _statistics = None
     _per_system = True
 
     def _add_observer(self, series_set, name, *args):
@@ -182,3 +183,33 @@ class Observed:
     def recorders(self):
         """name -> (t, x, values): float64 arrays, one row of values per recorded state."""
         return self._recorders.series(per_system=self._per_system) if self._recorders is not None else {}
+
+    # ---- device statistics (statistics.py) --------------------------------------------
+    def add_statistic(self, name, expression, stat="mean", every=1, nodes=slice(None)):
+        """Accumulate the statistic ``stat`` -- "mean", "var", "max", "min", "argmax", "argmin" (the
+        ``t`` of the first extremal sample) -- over time of the model expression ``expression`` at every
+        node, on the GPU (``statistics.py``): the current state is sample 1, then the state after every
+        ``every``-th step is a sample (a Simulation: where the post-processes run), all of one weight.
+        ``statistics[name] = (n, x, values[ncols])`` at the nodes ``nodes`` (a slice), an Ensemble's
+        ``(n, x, values[nsys, ncols])`` of this rank's members only; the fields never come to the host
+        for it."""
+        if self._statistics is None:
+            from .statistics import StatisticSet
+            self._statistics = StatisticSet(self.model, self._n_nodes)
+        self._add_observer(self._statistics, name, expression, stat, every, nodes)
+
+    def remove_statistic(self, name):
+        if self._statistics is None:
+            raise KeyError(name)
+        self._statistics.remove(name)
+
+    def reset_statistic(self, name):
+        """Drop the samples taken so far (a transient): the next due state is sample 1 again."""
+        if self._statistics is None:
+            raise KeyError(name)
+        self._statistics.reset(name)
+
+    @property
+    def statistics(self):
+        """name -> (n, x, values): the samples folded so far, float64 arrays over the nodes."""
+        return self._statistics.series(per_system=self._per_system) if self._statistics is not None else {}

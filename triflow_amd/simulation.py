@@ -106,6 +106,7 @@ class Simulation(Observed):
         self._container = None
         self._probes = None
         self._recorders = None
+        self._statistics = None
         self._iterator = self.compute()
 
     def _compute_one_step(self, t, fields, pars):
@@ -140,6 +141,8 @@ class Simulation(Observed):
                     self._record_on(self._probes)
                 if self._recorders is not None:
                     self._record_on(self._recorders)
+                if self._statistics is not None:
+                    self._record_on(self._statistics)
                 for pprocess in self.post_processes:
                     pprocess.function(self)
                 self.stream.emit(self)

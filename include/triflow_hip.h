@@ -153,7 +153,11 @@ int tf_matvec(tf_solver*, const double* v_flat, double* y_flat);     /* y = J @ 
 int tf_step_theta(tf_solver*, int32_t src, int32_t dst, double dt, double theta);
 /* alpha, gamma: [s][s] row major; b, b_pred: [s] (b_pred may be NULL);
  * err_out (may be NULL) receives ||U - U_pred||_inf, one scalar over all systems;
- * hook_after: apply the Dirichlet list to the result (fixed-step __call__) */
+ * hook_after: apply the Dirichlet list to the result (fixed-step __call__).
+ * The estimate is never finite when a state is not: NaN wins the maximum, as in np.linalg.norm.
+ * With a NaN in the input state of one system, tf_step_row fails (non-zero return: the
+ * factorisation meets a non-finite pivot block); tf_read_err after tf_step_row_queued returns
+ * NaN, and the next call that synchronises (tf_get_state, tf_sync) fails */
 int tf_step_row(tf_solver*, int32_t src, int32_t dst, double dt, int32_t s,
                 const double* alpha, const double* gamma, const double* b,
                 const double* b_pred, int32_t hook_after, double* err_out);
@@ -204,7 +208,10 @@ int tf_step_doubling(tf_solver*, int32_t src, int32_t dst, int32_t tmp, int32_t 
                      int32_t m, int32_t nfine, const tf_scheme* scheme, int32_t ord, double* err_out);
 /* ||state[a] - state[b]||_ord of every dependent variable, out[nsys][nvar]; ord = 2
  * or 0 (max norm): the error estimate of the step-doubling wrapper
- * (schemes.py:41-44) without bringing the fields to the host */
+ * (schemes.py:41-44) without bringing the fields to the host.  NaN propagates as in
+ * np.linalg.norm, for both values of ord: a NaN difference at any node makes that variable's
+ * and system's norm NaN (the maximum lets NaN win and keeps it), and only that one.  The maximum
+ * norm is exact (the bits of np.abs(a - b).max()); the 2-norm is within (N + 2) * 2^-53, relative */
 int tf_diff_norm(tf_solver*, int32_t slot_a, int32_t slot_b, int32_t ord, double* out);
 
 /* componentwise backward error max|b-Ax|/(|x|+|cJ||x|+|b|) measured on the first

@@ -174,14 +174,14 @@ __global__ void __launch_bounds__(256) tfk_diffnorm(TfNormArgs a) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         const double o = __shfl_xor(acc, off, 64);
-        acc = a.ord == 2 ? acc + o : (o > acc ? o : acc);
+        acc = a.ord == 2 ? acc + o : ((o > acc || o != o) ? o : acc);      // NaN wins and stays
     }
     __shared__ double part[4];
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < (int)(blockDim.x >> 6); ++w)
-            acc = a.ord == 2 ? acc + part[w] : (part[w] > acc ? part[w] : acc);
+            acc = a.ord == 2 ? acc + part[w] : ((part[w] > acc || part[w] != part[w]) ? part[w] : acc);
         a.partial[(int64_t)blockIdx.y * a.nblocks + blockIdx.x] = acc;
         if (a.status && blockIdx.x == 0 && blockIdx.y == 0) {
             double* tail = a.partial + (int64_t)gridDim.y * a.nblocks;

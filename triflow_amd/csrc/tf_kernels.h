@@ -553,6 +553,8 @@ TF_DEVICE void tfk_gather_elem(const TfGatherArgs& a, int64_t t) {
 
 // (a - b) of variable/system `vs` restricted to the slice of work item (blk, tid):
 // this thread's partial sum of squares (ord 2) or maximum (ord 0)
+// (the maximum: NaN wins and, once in a partial, stays -- like np.linalg.norm(inf) and tfk_vec_maxabs; the
+// folds of the partials in tfk_diffnorm and on the host, diff_norm, keep the same rule)
 TF_DEVICE double tfk_diffnorm_partial(const TfNormArgs& a, int vs, int blk, int tid, int nthreads) {
     const TfLayout& L = a.L;
     const int v = vs / L.nsys, e = vs - v * L.nsys;
@@ -565,7 +567,7 @@ TF_DEVICE double tfk_diffnorm_partial(const TfNormArgs& a, int vs, int blk, int 
         const int64_t s = (int64_t)v * L.plane + i * L.Ptot + (int64_t)e * L.P + p;
         const double d = a.a[s] - a.b[s];
         if (a.ord == 2) acc = tf_fma(d, d, acc);
-        else acc = tf_abs(d) > acc ? tf_abs(d) : acc;
+        else { const double m = tf_abs(d); acc = (m > acc || m != m) ? m : acc; }
     }
     return acc;
 }

@@ -93,7 +93,7 @@ void diff_norm(tf_solver* s, int32_t slot_a, int32_t slot_b, int32_t ord, double
         double acc = 0.0;
         for (int b = 0; b < nb; ++b) {
             const double v = part[(size_t)vs * nb + b];
-            acc = ord == 2 ? acc + v : (v > acc ? v : acc);
+            acc = ord == 2 ? acc + v : ((v > acc || v != v) ? v : acc);      // (NaN wins and stays)
         }
         const int v = vs / s->nsys, e = vs % s->nsys;
         out[(size_t)e * s->spec.nvar + v] = ord == 2 ? std::sqrt(acc) : acc;

@@ -330,6 +330,31 @@ int tf_stat_fetch(tf_stat*, int32_t which, double* out);
 /* the inverse of tf_stat_fetch: in[planes][nsys][N] become the planes of statistic `which` */
 int tf_stat_load(tf_stat*, int32_t which, const double* in);
 
+/* ---- device spectra: Fourier amplitudes of model expressions on a resident state slot ----
+ * code_object: the model's code object rebuilt with the generated spectrum block (codegen.lower_spectra;
+ * built with the solver's parameter layout and sweep segment), of which only tfk_spectrum_partial and
+ * tfk_spectrum_final are launched.  geometry[nspec][3]: the expression of the block (spectra may share
+ * one; the expressions are numbered in the order the spectra first use them), the number of modes
+ * (1 ... 64) and the rows of the spectrum's ring in device memory.  The modes themselves (each 0 ... N/2)
+ * are data of the handle: set_modes before the first record.  A record is queued on the solver's stream
+ * (no host wait unless the ring is full: then all of it comes over in one copy first) and writes one row
+ * [nsys][nmodes] of (re, im) pairs, c = sum over the nodes g of v_g exp(-2 pi i m g / N).  A spectrum
+ * set belongs to its solver: destroy it first. */
+typedef struct tf_spectrum tf_spectrum;
+int tf_spectrum_create(tf_solver*, const void* code_object, size_t code_size, int32_t nspec,
+                       const int32_t* geometry, int32_t nconst, tf_spectrum** out);
+void tf_spectrum_destroy(tf_spectrum* spectrum);
+int tf_spectrum_set_consts(tf_spectrum*, const double* values /*[nsys][nconst]*/, int32_t nconst);
+/* coordinates of the nodes (expressions that read x); ignored when the solver's model reads x itself */
+int tf_spectrum_set_x(tf_spectrum*, const double* x /*[nsys][N]*/);
+int tf_spectrum_set_modes(tf_spectrum*, int32_t which, const int32_t* modes, int32_t nmodes);
+int tf_spectrum_record(tf_spectrum*, int32_t which, int32_t slot);
+/* waits, then hands over up to max_rows rows of spectrum `which` not fetched before, oldest first,
+ * out[rows][nsys][nmodes][2] */
+int tf_spectrum_fetch(tf_spectrum*, int32_t which, double* out, int64_t max_rows, int64_t* rows);
+/* rows of spectrum `which` recorded and not fetched yet (no wait) */
+int tf_spectrum_pending(tf_spectrum*, int32_t which, int64_t* rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,15 @@ SIGNATURES = {
     "tf_stat_planes_of": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "tf_stat_fetch": (C.c_int, [C.c_void_p, C.c_int32, c_double_p]),
     "tf_stat_load": (C.c_int, [C.c_void_p, C.c_int32, c_double_p]),
+    "tf_spectrum_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, c_int32_p, C.c_int32,
+                                     C.POINTER(C.c_void_p)]),
+    "tf_spectrum_destroy": (None, [C.c_void_p]),
+    "tf_spectrum_set_consts": (C.c_int, [C.c_void_p, c_double_p, C.c_int32]),
+    "tf_spectrum_set_x": (C.c_int, [C.c_void_p, c_double_p]),
+    "tf_spectrum_set_modes": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.c_int32]),
+    "tf_spectrum_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "tf_spectrum_fetch": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int64, c_int64_p]),
+    "tf_spectrum_pending": (C.c_int, [C.c_void_p, C.c_int32, c_int64_p]),
 }
 
 
@@ -522,7 +531,7 @@ class DeviceSolver:
 
 
 class _DeviceObserver:
-    """What ``tf_probe``, ``tf_record`` and ``tf_stat`` share: a code object of expressions bound to one solver, the
+    """What ``tf_probe``, ``tf_record``, ``tf_stat`` and ``tf_spectrum`` share: a code object of expressions bound to one solver, the
     x plane and the host constants of the expressions.  ``_prefix``: of the C entry points, ``_noun``:
     what the error message calls the set."""
 
@@ -656,3 +665,34 @@ class DeviceStat(_DeviceObserver):
         """The inverse of ``fetch``."""
         a = _f64(planes, (self.planes[which], self.solver.nsys, self.solver.N))
         self._call("load", int(which), _dptr(a))
+
+
+class DeviceSpectrum(_DeviceObserver):
+    """``tf_spectrum``: the spectrum kernels of one spectrum set bound to one solver, the modes and the
+    rings."""
+
+    _prefix, _noun = "tf_spectrum", "spectrum"
+
+    def __init__(self, solver, code, geometry, modes, nconst):
+        """``geometry``: per spectrum ``(expression, number of modes, rows of the ring)``; ``modes``: per
+        spectrum, its modes (uploaded here: they are data of the handle, not of the code object)."""
+        g = np.ascontiguousarray(geometry, dtype=np.int32).reshape(-1, 3)
+        self.nmodes = [int(r[1]) for r in g]
+        self.fetched = 0                         # doubles that came to the host through fetch
+        self._create(solver, code, nconst, len(g), g.ctypes.data_as(c_int32_p), int(nconst))
+        for k, m in enumerate(modes):
+            m = np.ascontiguousarray(m, dtype=np.int32)
+            self._call("set_modes", k, m.ctypes.data_as(c_int32_p), int(m.size))
+
+    def record(self, which, slot):
+        self._call("record", int(which), int(slot))
+
+    def pending(self, which):
+        return self._pending(int(which))
+
+    def fetch(self, which):
+        """Every row of spectrum ``which`` recorded since its last fetch, ``[rows][nsys][nmodes]``
+        complex128 (waits for the stream)."""
+        raw = self._fetch(2 * self.nmodes[which], int(which))
+        self.fetched += raw.size
+        return np.ascontiguousarray(raw).view(np.complex128)

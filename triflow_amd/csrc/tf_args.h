@@ -419,12 +419,38 @@ struct TfStatArgs : TfNodeArgs {
     double t;                      // time of this sample (argmax / argmin)
     double* acc;                   // [tf_stat_planes(kind)] planes
 };
+
+// Device spectra (tf_spectrum.h, tf_rt_spectrum.cpp): Fourier amplitudes of model expressions.  Row of a
+// spectrum: c[i] = sum over the natural nodes g of v_g * exp(-2 pi i m_i g / N), v the expression `which`
+// of the spectrum block on a resident state slot, m_i the modes of the spectrum (a device buffer of the
+// handle: the code object does not know them).  tfk_spectrum_partial: grid (nsys * nblk, nseg), one thread
+// per segment of TF_PROBE_SEG nodes as tfk_probe_partial, one (re, im) pair per workgroup, mode and
+// system; tfk_spectrum_final: grid (nsys), reduces the partials of its system in a fixed order and writes
+// row `row` of the ring.
+// Modes of one spectrum.  The tables of a workgroup of tfk_spectrum_partial in LDS are the step twiddles
+// [TF_PROBE_SEG][modes] and the sums of its four wavefronts [4][modes], complex doubles: 192 bytes per
+// mode, 12 KiB at 64.  A CU holds 8 workgroups of 256 threads (32 wavefronts) and 160 KiB of LDS: at 64
+// modes the tables take 96 KiB and the registers decide how many workgroups are resident, at 128 they
+// would take 192 KiB and the LDS would.
+#define TF_SPEC_MAX_MODES 64
+struct TfSpectrumArgs : TfNodeArgs {
+    int which;                     // expression of the spectrum block (tf_eval_spectrum's first argument)
+    int nmodes;                    // 1 ... TF_SPEC_MAX_MODES
+    int nblk;                      // workgroups of tfk_spectrum_partial per system and segment row
+    int nseg;                      // segments of TF_PROBE_SEG nodes per chunk
+    int row;                       // row of the ring this launch writes (by value: the host counts)
+    int capacity;                  // rows of the ring
+    const int* modes;              // [nmodes], each 0 ... N / 2
+    double* partial;               // [nsys][nmodes][nseg * nblk] (re, im) pairs
+    double* ring;                  // [capacity][nsys][nmodes] (re, im) pairs
+};
 // (passed by value to kernels of code objects the host did not compile: the bytes are the contract)
 // (the base comes first and the members follow in their order: the sizes pin the bytes)
 static_assert(sizeof(TfNodeArgs) == 96, "TfNodeArgs changed its layout");
 static_assert(sizeof(TfProbeArgs) == 144, "TfProbeArgs changed its layout");
 static_assert(sizeof(TfRecordArgs) == 152, "TfRecordArgs changed its layout");
 static_assert(sizeof(TfStatArgs) == 136, "TfStatArgs changed its layout");
+static_assert(sizeof(TfSpectrumArgs) == 144, "TfSpectrumArgs changed its layout");
 
 // Kernel table: index = launch id used by the runtime, name = entry point in
 // the per-model code object (tf_entry_hip.h).  New entries go at the end: the
@@ -454,17 +480,22 @@ enum TfKernel {
 #define TF_KERNEL_NAMES_RECORD { "tfk_record" }
 // ... and the launch ids after TFK_COUNT, with a table of their own as well: the kernel of the statistics.
 // TFK_TOTAL is the number of kernels of a code object: what the runtime sizes and loops by.
-enum TfKernelMore { TFK_STAT = TFK_COUNT, TFK_TOTAL };
+// After it, the kernels of the spectra (TF_KERNEL_NAMES_SPECTRUM).
+enum TfKernelMore { TFK_STAT = TFK_COUNT, TFK_SPECTRUM_PARTIAL, TFK_SPECTRUM_FINAL, TFK_TOTAL };
 #define TF_KERNEL_NAMES_STAT { "tfk_stat" }
+#define TF_KERNEL_NAMES_SPECTRUM { "tfk_spectrum_partial", "tfk_spectrum_final" }
 static inline const char* tf_kernel_entry(int kernel) {
     static const char* const base[] = TF_KERNEL_NAMES;
     static const char* const rec[] = TF_KERNEL_NAMES_RECORD;
     static const char* const stat[] = TF_KERNEL_NAMES_STAT;
     static_assert(sizeof(base) / sizeof(base[0]) == TFK_RECORD, "TF_KERNEL_NAMES and TfKernel differ");
     static_assert(sizeof(rec) / sizeof(rec[0]) == TFK_COUNT - TFK_RECORD, "TF_KERNEL_NAMES_RECORD and TfKernel differ");
-    static_assert(sizeof(stat) / sizeof(stat[0]) == TFK_TOTAL - TFK_STAT, "TF_KERNEL_NAMES_STAT and TfKernelMore differ");
+    static const char* const spec[] = TF_KERNEL_NAMES_SPECTRUM;
+    static_assert(sizeof(stat) / sizeof(stat[0]) == TFK_SPECTRUM_PARTIAL - TFK_STAT, "TF_KERNEL_NAMES_STAT and TfKernelMore differ");
+    static_assert(sizeof(spec) / sizeof(spec[0]) == TFK_TOTAL - TFK_SPECTRUM_PARTIAL, "TF_KERNEL_NAMES_SPECTRUM and TfKernelMore differ");
     static_assert(TFK_TOTAL <= 64, "the timing mask has one bit per kernel");
     if (kernel < 0 || kernel >= TFK_TOTAL) return "";
+    if (kernel >= TFK_SPECTRUM_PARTIAL) return spec[kernel - TFK_SPECTRUM_PARTIAL];
     if (kernel >= TFK_STAT) return stat[kernel - TFK_STAT];
     return kernel < TFK_RECORD ? base[kernel] : rec[kernel - TFK_RECORD];
 }

@@ -10,6 +10,7 @@
 #include "tf_probe.h"
 #include "tf_record.h"
 #include "tf_stat.h"
+#include "tf_spectrum.h"
 
 #define TF_GID ((int)(blockIdx.x * blockDim.x + threadIdx.x))
 

@@ -105,7 +105,7 @@ class Ensemble(Observed):
         self._x = x
         self._member_pars = [[np.asarray(v)[e] if np.ndim(v) >= 1 and np.shape(v)[0] == self.nsys else v
                               for v in values] for e in range(self.nsys)]
-        self._probes, self._recorders, self._statistics, self._nsteps = None, None, None, 0
+        self._probes, self._recorders, self._statistics, self._spectra, self._nsteps = None, None, None, None, 0
 
     def step(self, dt):
         """One fixed step of every member (asynchronous: returns after the launches)."""
@@ -131,6 +131,8 @@ class Ensemble(Observed):
             self._record_on(self._recorders)
         if self._statistics is not None:
             self._record_on(self._statistics)
+        if self._spectra is not None:
+            self._record_on(self._spectra)
 
     # ---- device probes and recorders (observers.Observed) ---------------------------------
     _n_nodes = property(lambda self: self.N)
@@ -164,6 +166,8 @@ class Ensemble(Observed):
             self._recorders.close()
         if self._statistics is not None:
             self._statistics.close()
+        if self._spectra is not None:
+            self._spectra.close()
         self.solver.close()
 
     def state(self):

@@ -1,5 +1,5 @@
-"""Device observers: what the probes (``probes.py``), the recorders (``recorders.py``) and the statistics
-(``statistics.py``) share.
+"""Device observers: what the probes (``probes.py``), the recorders (``recorders.py``), the statistics
+(``statistics.py``) and the spectra (``spectra.py``) share.
 
 An observer evaluates expressions in the model's own string language at the nodes of a resident state
 slot and writes one row per record into a ring in device memory.  Both kinds go through the same node
@@ -63,7 +63,7 @@ class _Bound:
 class ObserverSet:
     """The code objects and handles of a set of observers: one handle per solver the set has run on, one
     code object per parameter layout / sweep segment of those solvers.  Subclasses: ``kind`` ("probe" /
-    "record" / "stat": ``compilers.build_observer_code_object``), ``_lower(mask) -> (block, spec)``,
+    "record" / "stat" / "spectrum": ``compilers.build_observer_code_object``), ``_lower(mask) -> (block, spec)``,
     ``_make_handle(solver, code, spec)`` and ``_flush()`` (every row still on the device to the series)."""
 
     kind = None
@@ -122,12 +122,14 @@ class ObserverSet:
 
 
 class Observed:
-    """``add_probe`` / ``add_recorder`` ... of a front end (``Simulation``, ``Ensemble``).  The front end
+    """``add_probe`` / ``add_recorder`` / ``add_statistic`` / ``add_spectrum`` ... of a front end
+    (``Simulation``, ``Ensemble``): reductions over space, decimated space-time pictures, reductions over
+    time and Fourier amplitudes over time.  The front end
     has ``model``, says how a set records its current state (``_record_on(series_set)``: also called after
-    every step for ``_probes``, ``_recorders`` and ``_statistics`` that are not None), how many nodes a system has
+    every step for ``_probes``, ``_recorders``, ``_statistics`` and ``_spectra`` that are not None), how many nodes a system has
     (``_n_nodes``) and whether its series keep the axis of the systems (``_per_system``)."""
 
-    _probes = _recorders = _statistics = None
+    _probes = _recorders = _statistics = _spectra = None
     _per_system = True
 
     def _add_observer(self, series_set, name, *args):
@@ -213,3 +215,30 @@ class Observed:
     def statistics(self):
         """name -> (n, x, values): the samples folded so far, float64 arrays over the nodes."""
         return self._statistics.series(per_system=self._per_system) if self._statistics is not None else {}
+
+    # ---- device spectra (spectra.py) ----------------------------------------------------
+    def add_spectrum(self, name, expression, modes, every=1, capacity=None):
+        """Record the Fourier amplitudes ``c[i] = sum_g v_g * exp(-2j * pi * modes[i] * g / N)`` of the
+        model expression ``expression`` (``v`` at the nodes ``g = 0 ... N - 1``) on the GPU
+        (``spectra.py``): ``np.fft.fft(v)[modes]``, unnormalised, no window, nothing subtracted (write
+        ``h - 1``).  ``periodic=False`` gets the same sum over the node sequence.  ``modes``: up to
+        ``spectra.MAX_MODES`` distinct integers in ``0 ... N // 2``.  A row now, then after every
+        ``every``-th step (a Simulation: where the post-processes run); ``capacity``: rows of the ring in
+        device memory (default 1024).  The series is ``spectra[name] = (t, k, c[rows, nmodes])`` with
+        the wavenumbers ``k = 2 * pi * modes / (N * dx)`` and ``c`` complex128, an Ensemble's ``(t, k,
+        c[rows, nsys, nmodes])`` with ``k [nsys, nmodes]`` when the members have grids of their own, of
+        this rank's members only; the fields never come to the host for it."""
+        if self._spectra is None:
+            from .spectra import SpectrumSet
+            self._spectra = SpectrumSet(self.model, self._n_nodes)
+        self._add_observer(self._spectra, name, expression, modes, every, capacity)
+
+    def remove_spectrum(self, name):
+        if self._spectra is None:
+            raise KeyError(name)
+        self._spectra.remove(name)
+
+    @property
+    def spectra(self):
+        """name -> (t, k, c): float64 times and wavenumbers, one complex128 row of c per recorded state."""
+        return self._spectra.series(per_system=self._per_system) if self._spectra is not None else {}

@@ -107,6 +107,7 @@ class Simulation(Observed):
         self._probes = None
         self._recorders = None
         self._statistics = None
+        self._spectra = None
         self._iterator = self.compute()
 
     def _compute_one_step(self, t, fields, pars):
@@ -143,6 +144,8 @@ class Simulation(Observed):
                     self._record_on(self._recorders)
                 if self._statistics is not None:
                     self._record_on(self._statistics)
+                if self._spectra is not None:
+                    self._record_on(self._spectra)
                 for pprocess in self.post_processes:
                     pprocess.function(self)
                 self.stream.emit(self)

@@ -355,6 +355,33 @@ int tf_spectrum_fetch(tf_spectrum*, int32_t which, double* out, int64_t max_rows
 /* rows of spectrum `which` recorded and not fetched yet (no wait) */
 int tf_spectrum_pending(tf_spectrum*, int32_t which, int64_t* rows);
 
+/* ---- device extrema: crests and troughs of model expressions on a resident state slot ----
+ * code_object: the model's code object rebuilt with the generated extrema block (codegen.lower_extrema;
+ * built with the solver's parameter layout and sweep segment), of which only tfk_extrema_count and
+ * tfk_extrema_write are launched.  geometry[next][4]: the expression of the block (observers may share
+ * one; the expressions are numbered in the order the observers first use them), the kind (0: max, 1: min),
+ * max_count (1 ... 8192) and the rows of the observer's ring in device memory (0: 1024 rows, or what 32 MB
+ * hold; a single row that is larger is refused).  thresholds[next]: a maximum counts when it is greater, a
+ * minimum when it is less (-inf / +inf: none).  Node g is a maximum iff v[g-1] < v[g] > v[g+1], strictly,
+ * and v[g] is finite; the neighbours wrap on a periodic grid, the end nodes of any other are never extrema.
+ * A record is queued on the solver's stream (no host wait unless the ring is full: then all of it comes
+ * over in one copy first) and writes one row [nsys][1 + 4 * max_count]: the number of extrema of the system
+ * (it may exceed max_count), then the first max_count of them in node order as (g, v[g-1], v[g], v[g+1]);
+ * the entries past the count are not written.  An extrema set belongs to its solver: destroy it first. */
+typedef struct tf_extrema tf_extrema;
+int tf_extrema_create(tf_solver*, const void* code_object, size_t code_size, int32_t next,
+                      const int32_t* geometry, const double* thresholds, int32_t nconst, tf_extrema** out);
+void tf_extrema_destroy(tf_extrema* extrema);
+int tf_extrema_set_consts(tf_extrema*, const double* values /*[nsys][nconst]*/, int32_t nconst);
+/* coordinates of the nodes (expressions that read x); ignored when the solver's model reads x itself */
+int tf_extrema_set_x(tf_extrema*, const double* x /*[nsys][N]*/);
+int tf_extrema_record(tf_extrema*, int32_t which, int32_t slot);
+/* waits, then hands over up to max_rows rows of observer `which` not fetched before, oldest first,
+ * out[rows][nsys][1 + 4 * max_count] */
+int tf_extrema_fetch(tf_extrema*, int32_t which, double* out, int64_t max_rows, int64_t* rows);
+/* rows of observer `which` recorded and not fetched yet (no wait) */
+int tf_extrema_pending(tf_extrema*, int32_t which, int64_t* rows);
+
 #ifdef __cplusplus
 }
 #endif

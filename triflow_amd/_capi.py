@@ -132,6 +132,14 @@ SIGNATURES = {
     "tf_spectrum_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "tf_spectrum_fetch": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int64, c_int64_p]),
     "tf_spectrum_pending": (C.c_int, [C.c_void_p, C.c_int32, c_int64_p]),
+    "tf_extrema_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, c_int32_p, c_double_p, C.c_int32,
+                                    C.POINTER(C.c_void_p)]),
+    "tf_extrema_destroy": (None, [C.c_void_p]),
+    "tf_extrema_set_consts": (C.c_int, [C.c_void_p, c_double_p, C.c_int32]),
+    "tf_extrema_set_x": (C.c_int, [C.c_void_p, c_double_p]),
+    "tf_extrema_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "tf_extrema_fetch": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int64, c_int64_p]),
+    "tf_extrema_pending": (C.c_int, [C.c_void_p, C.c_int32, c_int64_p]),
 }
 
 
@@ -531,7 +539,7 @@ class DeviceSolver:
 
 
 class _DeviceObserver:
-    """What ``tf_probe``, ``tf_record``, ``tf_stat`` and ``tf_spectrum`` share: a code object of expressions bound to one solver, the
+    """What ``tf_probe``, ``tf_record``, ``tf_stat``, ``tf_spectrum`` and ``tf_extrema`` share: a code object of expressions bound to one solver, the
     x plane and the host constants of the expressions.  ``_prefix``: of the C entry points, ``_noun``:
     what the error message calls the set."""
 
@@ -696,3 +704,31 @@ class DeviceSpectrum(_DeviceObserver):
         raw = self._fetch(2 * self.nmodes[which], int(which))
         self.fetched += raw.size
         return np.ascontiguousarray(raw).view(np.complex128)
+
+
+class DeviceExtrema(_DeviceObserver):
+    """``tf_extrema``: the extrema kernels of one extrema set bound to one solver, and the rings."""
+
+    _prefix, _noun = "tf_extrema", "extrema"
+
+    def __init__(self, solver, code, geometry, thresholds, nconst):
+        """``geometry``: per observer ``(expression, kind, max_count, rows of the ring or 0 for the
+        default)``; ``thresholds``: per observer, -inf (max) / +inf (min) for none."""
+        g = np.ascontiguousarray(geometry, dtype=np.int32).reshape(-1, 4)
+        th = _f64(thresholds).reshape(len(g))
+        self.max_count = [int(r[2]) for r in g]
+        self.fetched = 0                         # doubles that came to the host through fetch
+        self._create(solver, code, nconst, len(g), g.ctypes.data_as(c_int32_p), _dptr(th), int(nconst))
+
+    def record(self, which, slot):
+        self._call("record", int(which), int(slot))
+
+    def pending(self, which):
+        return self._pending(int(which))
+
+    def fetch(self, which):
+        """Every row of observer ``which`` recorded since its last fetch, ``[rows][nsys][1 + 4 * max_count]``:
+        the count, then ``(g, v[g-1], v[g], v[g+1])`` per entry (waits for the stream)."""
+        raw = self._fetch(1 + 4 * self.max_count[which], int(which))
+        self.fetched += raw.size
+        return raw

@@ -483,6 +483,33 @@ def lower_spectra(model, exprs, parvec_mask=0):
     return block, spec
 
 
+def lower_extrema(model, exprs, parvec_mask=0):
+    """Device extrema -> ``(block, spec)``: the C block that follows the model's own translation unit
+    (``TF_NEXT`` ... and ``tf_eval_extrema``, read by csrc/tf_extrema.h; expression ``k`` is case ``k``)
+    and the constants the runtime needs.  Lowered as the other observers are (``_lower_node_expressions``):
+    the per-node values are the bits NumPy computes from the printed expressions; the host constants go
+    into the extrema's own argument buffer (``spec["host_consts"]``).  Kind, threshold, ``max_count`` and
+    ``every`` are not part of the block: they are launch arguments, and sets that differ only in them
+    share a code object."""
+    lines, out, hc_list, uses_x, pars = _lower_node_expressions(model, exprs, parvec_mask)
+    lines += ["    switch (k) {"]
+    lines += ["    case %d: return %s;" % (i, c) for i, c in enumerate(out)]
+    lines += ["    default: return 0.0;", "    }"]
+    block = "\n".join([
+        "// device extrema, generated by triflow_amd.codegen.lower_extrema -- do not edit",
+        "// " + " ; ".join(str(e) for e in exprs),
+        "#define TF_NEXT %d" % len(out),
+        "#define TF_NEXT_HC %d" % len(hc_list),
+        "#define TF_EXT_USES_X %d" % (1 if uses_x else 0),
+        "TF_DEVICE double tf_eval_extrema(int k, const double (&w)[TF_NVAR + TF_NH][2 * TF_MP + 1], "
+        "const double* par, const double* tf_hc, double dx, double xc) {",
+        "\n".join(lines),
+        "}",
+        ""])
+    spec = dict(next=len(out), host_consts=hc_list, pars=pars, uses_x=int(uses_x))
+    return block, spec
+
+
 def _proportional_entries(model, j_uniform):
     """Jacobian entries that are an exact power-of-two multiple of an earlier node-dependent
     entry (``-q*dxT/h`` differentiated with respect to ``T_m1`` and ``T_p1``; ``We*h*dxxxh`` with

@@ -51,9 +51,10 @@ HIPCC_FLAGS = [*os.environ.get("TRIFLOW_HIPCC_OPT", "-O3").split(), "-std=c++17"
 #: translation units of the host runtime (see the header of csrc/tf_solver.h)
 RUNTIME_SOURCES = ("tf_rt_plan.cpp", "tf_rt_io.cpp", "tf_rt_steps.cpp", "tf_rt_diag.cpp",
                    "tf_solver_sweeps.cpp", "tf_solver_linear.cpp", "tf_rt_probe.cpp", "tf_rt_record.cpp",
-                   "tf_rt_stat.cpp", "tf_rt_spectrum.cpp")
+                   "tf_rt_stat.cpp", "tf_rt_spectrum.cpp", "tf_rt_extrema.cpp")
 _SKELETON = ("tf_args.h", "tf_math.h", "tf_kernels.h", "tf_crs.h", "tf_coop_hip.h", "tf_cr2_hip.h", "tf_cr3_hip.h",
-             "tf_node.h", "tf_probe.h", "tf_record.h", "tf_stat.h", "tf_spectrum.h", "tf_entry_hip.h")
+             "tf_node.h", "tf_probe.h", "tf_record.h", "tf_stat.h", "tf_spectrum.h", "tf_extrema.h",
+             "tf_entry_hip.h")
 _TU_HEAD = ('#include <hip/hip_runtime.h>\n'
             '#define TF_DEVICE __device__ __forceinline__\n'
             '%s'
@@ -123,7 +124,7 @@ def resource_usage(hsaco_path):
 def _compile_code_object(model, source, tag, hsaco, observer=None):
     """hipcc on the generated translation unit -> ``hsaco`` (+ source and resource table next to it).
     ``observer``: the unit carries an observer's block (build_observer_code_object) and this is its kind,
-    "probe", "record", "stat" or "spectrum": only the kernels ``tfk_<kind>*`` of that object are ever launched, so
+    "probe", "record", "stat", "spectrum" or "extrema": only the kernels ``tfk_<kind>*`` of that object are ever launched, so
     there is no second build for the spill gate -- one of them that spills is refused instead."""
     global BUILD_COUNT
     BUILD_COUNT += 1
@@ -262,11 +263,11 @@ def build_code_object(model, parvec_mask=0, seg=None, sweep_block=None):
 
 def build_observer_code_object(model, block, kind, parvec_mask=0, seg=8, sweep_block=256):
     """The model's translation unit followed by the block of an observer of ``kind`` "probe"
-    (codegen.lower_probes), "record" (codegen.lower_records), "stat" (codegen.lower_statistics) or
-    "spectrum" (codegen.lower_spectra) -> path of the cached code object, of which only the kernels ``tfk_<kind>*`` are launched.  Same parameter
+    (codegen.lower_probes), "record" (codegen.lower_records), "stat" (codegen.lower_statistics),
+    "spectrum" (codegen.lower_spectra) or "extrema" (codegen.lower_extrema) -> path of the cached code object, of which only the kernels ``tfk_<kind>*`` are launched.  Same parameter
     layout and sweep segment as the solver's own code object: the observer's kernels read that solver's
     planes and parameter slots."""
-    if kind not in ("probe", "record", "stat", "spectrum"):
+    if kind not in ("probe", "record", "stat", "spectrum", "extrema"):
         raise ValueError("unknown kind of observer %r" % (kind,))
     body, _ = codegen.lower_model(model, parvec_mask=parvec_mask, seg=seg, sweep_block=sweep_block)
     source = _TU_HEAD % "" + body + block + _TU_TAIL

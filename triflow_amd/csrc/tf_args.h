@@ -444,6 +444,31 @@ struct TfSpectrumArgs : TfNodeArgs {
     double* partial;               // [nsys][nmodes][nseg * nblk] (re, im) pairs
     double* ring;                  // [capacity][nsys][nmodes] (re, im) pairs
 };
+
+// Device extrema (tf_extrema.h, tf_rt_extrema.cpp): the crests or troughs of a model expression, a row of
+// variable length in node order.  Node g is an extremum of kind max iff v[g-1] < v[g] > v[g+1] (strictly;
+// min: both reversed) and v[g] is finite and beyond `threshold` (v > threshold, min: v < threshold; the host
+// passes -inf / +inf for "no threshold"); the neighbours wrap on a periodic grid, nodes 0 and N-1 of any
+// other grid are never extrema.  tfk_extrema_count: grid (nsys * nblk), thread = chunk, the extrema of every
+// chunk and of every workgroup; tfk_extrema_write: same grid, an exclusive integer scan of those counts gives
+// every chunk its place in the row, the walk is repeated and the first max_count entries are stored.
+// Row of the ring, per system: [0] the number of extrema found (may exceed max_count), then max_count
+// entries (g, v[g-1], v[g], v[g+1]); all doubles (node indices and counts are exact).
+#define TF_EXT_MAX 0
+#define TF_EXT_MIN 1
+#define TF_EXT_MAX_COUNT 8192
+struct TfExtremaArgs : TfNodeArgs {
+    int which;                     // expression of the extrema block (tf_eval_extrema's first argument)
+    int kind;                      // TF_EXT_MAX / TF_EXT_MIN
+    int max_count;                 // entries of a row, 1 ... TF_EXT_MAX_COUNT
+    int nblk;                      // workgroups per system
+    int row;                       // row of the ring this launch writes (by value: the host counts)
+    int capacity;                  // rows of the ring
+    double threshold;              // -inf (max) / +inf (min): none
+    int* counts;                   // [nsys][nblk * 256] extrema per chunk
+    int* sums;                     // [nsys][nblk] extrema per workgroup
+    double* ring;                  // [capacity][nsys][1 + 4 * max_count]
+};
 // (passed by value to kernels of code objects the host did not compile: the bytes are the contract)
 // (the base comes first and the members follow in their order: the sizes pin the bytes)
 static_assert(sizeof(TfNodeArgs) == 96, "TfNodeArgs changed its layout");
@@ -451,6 +476,7 @@ static_assert(sizeof(TfProbeArgs) == 144, "TfProbeArgs changed its layout");
 static_assert(sizeof(TfRecordArgs) == 152, "TfRecordArgs changed its layout");
 static_assert(sizeof(TfStatArgs) == 136, "TfStatArgs changed its layout");
 static_assert(sizeof(TfSpectrumArgs) == 144, "TfSpectrumArgs changed its layout");
+static_assert(sizeof(TfExtremaArgs) == 152, "TfExtremaArgs changed its layout");
 
 // Kernel table: index = launch id used by the runtime, name = entry point in
 // the per-model code object (tf_entry_hip.h).  New entries go at the end: the
@@ -480,10 +506,13 @@ enum TfKernel {
 #define TF_KERNEL_NAMES_RECORD { "tfk_record" }
 // ... and the launch ids after TFK_COUNT, with a table of their own as well: the kernel of the statistics.
 // TFK_TOTAL is the number of kernels of a code object: what the runtime sizes and loops by.
-// After it, the kernels of the spectra (TF_KERNEL_NAMES_SPECTRUM).
-enum TfKernelMore { TFK_STAT = TFK_COUNT, TFK_SPECTRUM_PARTIAL, TFK_SPECTRUM_FINAL, TFK_TOTAL };
+// After it, the kernels of the spectra (TF_KERNEL_NAMES_SPECTRUM), then those of the extrema
+// (TF_KERNEL_NAMES_EXTREMA).
+enum TfKernelMore { TFK_STAT = TFK_COUNT, TFK_SPECTRUM_PARTIAL, TFK_SPECTRUM_FINAL,
+                    TFK_EXTREMA_COUNT, TFK_EXTREMA_WRITE, TFK_TOTAL };
 #define TF_KERNEL_NAMES_STAT { "tfk_stat" }
 #define TF_KERNEL_NAMES_SPECTRUM { "tfk_spectrum_partial", "tfk_spectrum_final" }
+#define TF_KERNEL_NAMES_EXTREMA { "tfk_extrema_count", "tfk_extrema_write" }
 static inline const char* tf_kernel_entry(int kernel) {
     static const char* const base[] = TF_KERNEL_NAMES;
     static const char* const rec[] = TF_KERNEL_NAMES_RECORD;
@@ -492,9 +521,12 @@ static inline const char* tf_kernel_entry(int kernel) {
     static_assert(sizeof(rec) / sizeof(rec[0]) == TFK_COUNT - TFK_RECORD, "TF_KERNEL_NAMES_RECORD and TfKernel differ");
     static const char* const spec[] = TF_KERNEL_NAMES_SPECTRUM;
     static_assert(sizeof(stat) / sizeof(stat[0]) == TFK_SPECTRUM_PARTIAL - TFK_STAT, "TF_KERNEL_NAMES_STAT and TfKernelMore differ");
-    static_assert(sizeof(spec) / sizeof(spec[0]) == TFK_TOTAL - TFK_SPECTRUM_PARTIAL, "TF_KERNEL_NAMES_SPECTRUM and TfKernelMore differ");
+    static const char* const ext[] = TF_KERNEL_NAMES_EXTREMA;
+    static_assert(sizeof(spec) / sizeof(spec[0]) == TFK_EXTREMA_COUNT - TFK_SPECTRUM_PARTIAL, "TF_KERNEL_NAMES_SPECTRUM and TfKernelMore differ");
+    static_assert(sizeof(ext) / sizeof(ext[0]) == TFK_TOTAL - TFK_EXTREMA_COUNT, "TF_KERNEL_NAMES_EXTREMA and TfKernelMore differ");
     static_assert(TFK_TOTAL <= 64, "the timing mask has one bit per kernel");
     if (kernel < 0 || kernel >= TFK_TOTAL) return "";
+    if (kernel >= TFK_EXTREMA_COUNT) return ext[kernel - TFK_EXTREMA_COUNT];
     if (kernel >= TFK_SPECTRUM_PARTIAL) return spec[kernel - TFK_SPECTRUM_PARTIAL];
     if (kernel >= TFK_STAT) return stat[kernel - TFK_STAT];
     return kernel < TFK_RECORD ? base[kernel] : rec[kernel - TFK_RECORD];

@@ -11,6 +11,7 @@
 #include "tf_record.h"
 #include "tf_stat.h"
 #include "tf_spectrum.h"
+#include "tf_extrema.h"
 
 #define TF_GID ((int)(blockIdx.x * blockDim.x + threadIdx.x))
 

@@ -12,6 +12,7 @@
 //   tf_rt_record.cpp       device recorders (tf_record_*) } end of this file, is what they share
 //   tf_rt_stat.cpp         device statistics (tf_stat_*)  }
 //   tf_rt_spectrum.cpp     device spectra (tf_spectrum_*) }
+//   tf_rt_extrema.cpp      device extrema (tf_extrema_*)  }
 #pragma once
 #include "../../include/triflow_hip.h"
 #include "tf_args.h"
@@ -599,7 +600,7 @@ struct tf_solver {
     void check_status(const int* have_flag = nullptr, const double* have_worst = nullptr);
 };
 
-// What the device observers (tf_probe, tf_record, tf_stat, tf_spectrum) share.  An observer is one more code object of the solver's
+// What the device observers (tf_probe, tf_record, tf_stat, tf_spectrum, tf_extrema) share.  An observer is one more code object of the solver's
 // model -- the model's translation unit plus a generated block of expressions -- of which only the
 // observer's own kernels are launched, on the solver's stream, on one of its state slots.  Here: the inputs
 // of the node core (TfNodeArgs; csrc/tf_node.h) and the launch.  Rings and copies are the observer's own.

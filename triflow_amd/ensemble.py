@@ -106,6 +106,7 @@ class Ensemble(Observed):
         self._member_pars = [[np.asarray(v)[e] if np.ndim(v) >= 1 and np.shape(v)[0] == self.nsys else v
                               for v in values] for e in range(self.nsys)]
         self._probes, self._recorders, self._statistics, self._spectra, self._nsteps = None, None, None, None, 0
+        self._extrema = None
 
     def step(self, dt):
         """One fixed step of every member (asynchronous: returns after the launches)."""
@@ -133,6 +134,8 @@ class Ensemble(Observed):
             self._record_on(self._statistics)
         if self._spectra is not None:
             self._record_on(self._spectra)
+        if self._extrema is not None:
+            self._record_on(self._extrema)
 
     # ---- device probes and recorders (observers.Observed) ---------------------------------
     _n_nodes = property(lambda self: self.N)
@@ -168,6 +171,8 @@ class Ensemble(Observed):
             self._statistics.close()
         if self._spectra is not None:
             self._spectra.close()
+        if self._extrema is not None:
+            self._extrema.close()
         self.solver.close()
 
     def state(self):

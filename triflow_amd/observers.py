@@ -1,5 +1,5 @@
 """Device observers: what the probes (``probes.py``), the recorders (``recorders.py``), the statistics
-(``statistics.py``) and the spectra (``spectra.py``) share.
+(``statistics.py``), the spectra (``spectra.py``) and the extrema (``extrema.py``) share.
 
 An observer evaluates expressions in the model's own string language at the nodes of a resident state
 slot and writes one row per record into a ring in device memory.  Both kinds go through the same node
@@ -63,7 +63,7 @@ class _Bound:
 class ObserverSet:
     """The code objects and handles of a set of observers: one handle per solver the set has run on, one
     code object per parameter layout / sweep segment of those solvers.  Subclasses: ``kind`` ("probe" /
-    "record" / "stat" / "spectrum": ``compilers.build_observer_code_object``), ``_lower(mask) -> (block, spec)``,
+    "record" / "stat" / "spectrum" / "extrema": ``compilers.build_observer_code_object``), ``_lower(mask) -> (block, spec)``,
     ``_make_handle(solver, code, spec)`` and ``_flush()`` (every row still on the device to the series)."""
 
     kind = None
@@ -122,14 +122,14 @@ class ObserverSet:
 
 
 class Observed:
-    """``add_probe`` / ``add_recorder`` / ``add_statistic`` / ``add_spectrum`` ... of a front end
-    (``Simulation``, ``Ensemble``): reductions over space, decimated space-time pictures, reductions over
-    time and Fourier amplitudes over time.  The front end
+    """``add_probe`` / ``add_recorder`` / ``add_statistic`` / ``add_spectrum`` / ``add_extrema`` ... of a
+    front end (``Simulation``, ``Ensemble``): reductions over space, decimated space-time pictures,
+    reductions over time, Fourier amplitudes over time and the crests and troughs over time.  The front end
     has ``model``, says how a set records its current state (``_record_on(series_set)``: also called after
-    every step for ``_probes``, ``_recorders``, ``_statistics`` and ``_spectra`` that are not None), how many nodes a system has
+    every step for ``_probes``, ``_recorders``, ``_statistics``, ``_spectra`` and ``_extrema`` that are not None), how many nodes a system has
     (``_n_nodes``) and whether its series keep the axis of the systems (``_per_system``)."""
 
-    _probes = _recorders = _statistics = _spectra = None
+    _probes = _recorders = _statistics = _spectra = _extrema = None
     _per_system = True
 
     def _add_observer(self, series_set, name, *args):
@@ -242,3 +242,36 @@ class Observed:
     def spectra(self):
         """name -> (t, k, c): float64 times and wavenumbers, one complex128 row of c per recorded state."""
         return self._spectra.series(per_system=self._per_system) if self._spectra is not None else {}
+
+    # ---- device extrema (extrema.py) ----------------------------------------------------
+    def add_extrema(self, name, expression, kind="max", threshold=None, every=1, max_count=256, capacity=None,
+                    refine=True):
+        """Record the local extrema of the model expression ``expression`` (``v`` at the nodes ``g = 0 ...
+        N - 1``) on the GPU (``extrema.py``): node ``g`` is a "max" iff ``v[g-1] < v[g] > v[g+1]``,
+        strictly (a "min": reversed), ``v[g]`` is finite and, with a ``threshold``, ``v[g] > threshold``
+        (a "min": ``<``) -- ``scipy.signal.argrelextrema(v, np.greater, mode="wrap")`` on a periodic grid,
+        ``mode="clip"`` on any other (nodes ``0`` and ``N - 1`` are never extrema there).  A NaN compares
+        false; a plateau of exactly equal values is not reported.  A row now, then after every
+        ``every``-th step (a Simulation: where the post-processes run); ``capacity``: rows of the ring in
+        device memory (default 1024, or what 32 MB hold).  The series is ``extrema[name] = (t, n, g, x,
+        v)``: ``n[rows]`` (int64) the number of extrema found, which may exceed ``max_count``; the first
+        ``min(n, max_count)`` in ascending node order: ``g[rows, max_count]`` (int64) the node, -1 past
+        them, ``x`` and ``v`` (float64, NaN past them) the vertex of the parabola through the node and its
+        neighbours (``refine=True``) or the node's own ``x`` and ``v[g]`` (``refine=False``).  An
+        Ensemble's: ``n[rows, nsys]`` and ``g, x, v [rows, nsys, max_count]``, of this rank's members only;
+        the fields never come to the host for it."""
+        if self._extrema is None:
+            from .extrema import ExtremaSet
+            self._extrema = ExtremaSet(self.model, self._n_nodes)
+        self._add_observer(self._extrema, name, expression, kind, threshold, every, max_count, capacity, refine)
+
+    def remove_extrema(self, name):
+        if self._extrema is None:
+            raise KeyError(name)
+        self._extrema.remove(name)
+
+    @property
+    def extrema(self):
+        """name -> (t, n, g, x, v): float64 times, int64 counts and nodes, float64 positions and values,
+        one row per recorded state."""
+        return self._extrema.series(per_system=self._per_system) if self._extrema is not None else {}

@@ -108,6 +108,7 @@ class Simulation(Observed):
         self._recorders = None
         self._statistics = None
         self._spectra = None
+        self._extrema = None
         self._iterator = self.compute()
 
     def _compute_one_step(self, t, fields, pars):
@@ -146,6 +147,8 @@ class Simulation(Observed):
                     self._record_on(self._statistics)
                 if self._spectra is not None:
                     self._record_on(self._spectra)
+                if self._extrema is not None:
+                    self._record_on(self._extrema)
                 for pprocess in self.post_processes:
                     pprocess.function(self)
                 self.stream.emit(self)

@@ -16,6 +16,7 @@ identically one (``compilers.py:204-205``), ``Max``/``Min`` are
 import ast
 import hashlib
 import inspect
+import os
 
 import numpy as np
 from sympy import lambdify
@@ -222,6 +223,28 @@ def _stencil_names(fields, pars, mp, parvec_mask):
     return names, decls, uniform
 
 
+def block_mask(nvar, pat_eq, pat_var):
+    """``mask[eq][var]``: the entries of an nvar x nvar block of the banded solver that can be non-zero.
+
+    The Jacobian pattern, united over the stencil offsets and with the diagonal added (A = I - c J),
+    is a relation G on the variables; the patterns inside its reflexive-transitive closure G* are
+    closed under sums, products and inverses, so every block the elimination forms lies in G*
+    (DESIGN.md section 4).  ``TRIFLOW_BLOCK_MASK=0`` gives the all-true mask: the dense code, for
+    A/B runs.  The mask is part of the generated header, so the caches keyed by it follow."""
+    if os.environ.get("TRIFLOW_BLOCK_MASK", "1") == "0":
+        return [[True] * nvar for _ in range(nvar)]
+    m = [[r == c for c in range(nvar)] for r in range(nvar)]
+    for e, v in zip(pat_eq, pat_var):
+        m[e][v] = True
+    for k in range(nvar):                           # Warshall
+        for r in range(nvar):
+            if m[r][k]:
+                for c in range(nvar):
+                    if m[k][c]:
+                        m[r][c] = True
+    return m
+
+
 def lower_model(model, parvec_mask=0, seg=8, sweep_block=64):
     """Returns ``(source, spec)``: the per-model translation unit (without the
     skeleton includes' contents) and the dict of constants the runtime needs."""
@@ -293,6 +316,8 @@ def lower_model(model, parvec_mask=0, seg=8, sweep_block=64):
         vals = ", ".join(str(v) for v in values) if values else "0"
         return "static constexpr %s %s[%d] = {%s};" % (ctype, name, max(len(values), 1), vals)
 
+    blk_nz = block_mask(nvar, pat_eq, pat_var)
+    blk_full = all(all(row) for row in blk_nz)
     hc_list = [src_ for src_, _ in sorted(host_consts.items(), key=lambda kv: kv[1])]
     par_is_vec = [1 if (parvec_mask >> k) & 1 else 0 for k in range(len(pars))] + [0] * len(hc_list)
     if len(pars) + len(hc_list) > 16:
@@ -309,6 +334,10 @@ def lower_model(model, parvec_mask=0, seg=8, sweep_block=64):
         "#define TF_SWEEP_BLOCK %d" % sweep_block,
         "#define TF_USES_X %d" % (1 if uses_x else 0),
         arr("tf_pat_eq", pat_eq), arr("tf_pat_var", pat_var), arr("tf_pat_off", pat_off),
+        "// entries of a solver block that can be non-zero (block_mask): [equation][variable]",
+        "#define TF_BLK_FULL %d" % (1 if blk_full else 0),
+        "static constexpr bool tf_blk_nz[%d][%d] = {%s};" % (
+            nvar, nvar, ", ".join("{%s}" % ", ".join("true" if v else "false" for v in row) for row in blk_nz)),
         arr("tf_par_is_vec", par_is_vec, "bool"),
         arr("tf_j_uniform", j_uniform, "bool"),
         arr("tf_j_alias", j_alias), arr("tf_j_alias_scale", [_dbl(v) for v in j_alias_scale], "double"),
@@ -331,7 +360,7 @@ def lower_model(model, parvec_mask=0, seg=8, sweep_block=64):
                 sweep_block=sweep_block, uses_x=int(uses_x), parvec_mask=int(parvec_mask),
                 b2=mp * nvar, pat_eq=pat_eq, pat_var=pat_var, pat_off=pat_off, j_uniform=j_uniform,
                 j_alias=j_alias, j_alias_scale=j_alias_scale,
-                fields=fields, pars=pars)
+                blk_nz=blk_nz, fields=fields, pars=pars)
     return src, spec
 
 

@@ -638,70 +638,117 @@ TF_DEVICE void tf_blk_copy(double (&d)[B][B], const double (&s)[B][B]) {
 #pragma unroll
         for (int c = 0; c < B; ++c) d[r][c] = s[r][c];
 }
+// ---- the block mask ---------------------------------------------------------
+// tf_blk_nz (generated, codegen.block_mask): the entries of a TF_NVAR x TF_NVAR block that can be
+// non-zero -- the reflexive-transitive closure G* of the Jacobian pattern over the variables.
+// Patterns inside G* are closed under sums, products and inverses, so every block of the level-1
+// elimination (D, D^-1, L, U~, the spike columns, the tips) is an exact zero outside G*, and the
+// helpers below neither compute nor read those entries: results there are a literal 0.0, the
+// terms that are left keep their order, so the other entries keep their bits.
+// The trait is keyed by the block size.  Blocks of any other size are dense (the reduced levels of
+// a model with TF_MP == 2).  For TF_MP == 1 the reduced levels have TF_B2 == TF_NVAR: their
+// blocks are Schur complements and products of level-1 blocks and lie inside G* as well, so the
+// model's mask holds for them too.  With TF_BLK_FULL every test below is the constant true and
+// the helpers are the dense code.
+template <int B> struct TfMask {
+    static constexpr bool FULL = true;
+    TF_DEVICE_M static constexpr bool nz(int, int) { return true; }
+    TF_DEVICE_M static constexpr bool same(int, int) { return true; }
+};
+#if defined(TF_BLK_FULL) && !TF_BLK_FULL
+template <> struct TfMask<TF_NVAR> {
+    static constexpr bool FULL = false;
+    TF_DEVICE_M static constexpr bool nz(int r, int c) { return tf_blk_nz[r][c]; }
+    // rows of one class (mutually reachable variables: an irreducible diagonal block) have the
+    // same pattern
+    TF_DEVICE_M static constexpr bool same(int r, int c) { return tf_blk_nz[r][c] && tf_blk_nz[c][r]; }
+};
+#endif
+
 // C -= A * Bm
 template <int B>
 TF_DEVICE void tf_mm_sub(double (&C)[B][B], const double (&A)[B][B], const double (&Bm)[B][B]) {
+    typedef TfMask<B> M;
 #pragma unroll
     for (int r = 0; r < B; ++r)
 #pragma unroll
         for (int c = 0; c < B; ++c) {
+            if (!M::nz(r, c)) { C[r][c] = 0.0; continue; }
             double acc = C[r][c];
 #pragma unroll
-            for (int k = 0; k < B; ++k) acc = tf_fma(-A[r][k], Bm[k][c], acc);
+            for (int k = 0; k < B; ++k)
+                if (M::nz(r, k) && M::nz(k, c)) acc = tf_fma(-A[r][k], Bm[k][c], acc);
             C[r][c] = acc;
         }
 }
 // C = A * Bm
 template <int B>
 TF_DEVICE void tf_mm(double (&C)[B][B], const double (&A)[B][B], const double (&Bm)[B][B]) {
+    typedef TfMask<B> M;
 #pragma unroll
     for (int r = 0; r < B; ++r)
 #pragma unroll
         for (int c = 0; c < B; ++c) {
             double acc = 0.0;
 #pragma unroll
-            for (int k = 0; k < B; ++k) acc = tf_fma(A[r][k], Bm[k][c], acc);
+            for (int k = 0; k < B; ++k)
+                if (M::nz(r, c) && M::nz(r, k) && M::nz(k, c)) acc = tf_fma(A[r][k], Bm[k][c], acc);
             C[r][c] = acc;
         }
 }
 template <int B>
 TF_DEVICE void tf_mv_sub(double (&y)[B], const double (&A)[B][B], const double (&x)[B]) {
+    typedef TfMask<B> M;
 #pragma unroll
     for (int r = 0; r < B; ++r) {
         double acc = y[r];
 #pragma unroll
-        for (int k = 0; k < B; ++k) acc = tf_fma(-A[r][k], x[k], acc);
+        for (int k = 0; k < B; ++k)
+            if (M::nz(r, k)) acc = tf_fma(-A[r][k], x[k], acc);
         y[r] = acc;
     }
 }
 template <int B>
 TF_DEVICE void tf_mv(double (&y)[B], const double (&A)[B][B], const double (&x)[B]) {
+    typedef TfMask<B> M;
 #pragma unroll
     for (int r = 0; r < B; ++r) {
         double acc = 0.0;
 #pragma unroll
-        for (int k = 0; k < B; ++k) acc = tf_fma(A[r][k], x[k], acc);
+        for (int k = 0; k < B; ++k)
+            if (M::nz(r, k)) acc = tf_fma(A[r][k], x[k], acc);
         y[r] = acc;
     }
 }
 
 // Gauss-Jordan inverse with partial (row) pivoting, all in registers.
+// Under a mask the pivot of column k is searched among the rows of k's class only (pivoting
+// inside the irreducible diagonal blocks, as block-triangular solvers do it): rows of one class
+// have the same pattern, so the exchange keeps `a` and `inv` inside G*, and an elimination
+// a[r] -= a[r][k] a[k] with (r, k) and (k, c) in G* lands on (r, c) in G* (transitivity): every
+// intermediate matrix stays inside G*.  Entries outside it are never touched and stay the
+// literal zeros they start as.
 template <int B>
 TF_DEVICE bool tf_blk_inverse(const double (&A)[B][B], double (&inv)[B][B]) {
+    typedef TfMask<B> M;
     double a[B][B];
-    tf_blk_copy<B>(a, A);
 #pragma unroll
     for (int r = 0; r < B; ++r)
 #pragma unroll
-        for (int c = 0; c < B; ++c) inv[r][c] = (r == c) ? 1.0 : 0.0;
+        for (int c = 0; c < B; ++c) {
+            a[r][c] = M::nz(r, c) ? A[r][c] : 0.0;
+            inv[r][c] = (r == c) ? 1.0 : 0.0;
+        }
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < B; ++k) {
 #pragma unroll
         for (int r = k + 1; r < B; ++r) {          // bubble the largest |a[r][k]| up to row k
+            if (!M::same(r, k)) continue;
             const bool sw = tf_abs(a[r][k]) > tf_abs(a[k][k]);
 #pragma unroll
             for (int c = 0; c < B; ++c) {
+                if (!M::nz(k, c)) continue;
                 const double t0 = a[k][c], t1 = a[r][c];
                 a[k][c] = sw ? t1 : t0;
                 a[r][c] = sw ? t0 : t1;
@@ -714,13 +761,15 @@ TF_DEVICE bool tf_blk_inverse(const double (&A)[B][B], double (&inv)[B][B]) {
         ok = ok && (piv != 0.0) && tf_finite(piv);
         const double rp = 1.0 / piv;
 #pragma unroll
-        for (int c = 0; c < B; ++c) { a[k][c] *= rp; inv[k][c] *= rp; }
+        for (int c = 0; c < B; ++c)
+            if (M::nz(k, c)) { a[k][c] *= rp; inv[k][c] *= rp; }
 #pragma unroll
         for (int r = 0; r < B; ++r) {
-            if (r == k) continue;
+            if (r == k || !M::nz(r, k)) continue;
             const double f = a[r][k];
 #pragma unroll
             for (int c = 0; c < B; ++c) {
+                if (!M::nz(k, c)) continue;
                 a[r][c] = tf_fma(-f, a[k][c], a[r][c]);
                 inv[r][c] = tf_fma(-f, inv[k][c], inv[r][c]);
             }
@@ -756,6 +805,9 @@ struct TfRowsL1 {
     // scalar equations: partial pivoting over the band inside the chunk interior
     // (rows are exchanged, so U widens to 2*MP like LAPACK's gbtrf)
     static constexpr bool PIVOT = TF_NVAR == 1;
+    // the stored factors (Ut, Et) and the exchange slots of a split walk leave out the entries
+    // outside the block mask: those planes are neither written nor read (tf_kept)
+    static constexpr bool MASKED = true;
     const TfLevelArgs& a;
     int pg, e, p, len, start;
     TfJUniform ju;                 // the node-independent entries: not read back
@@ -836,6 +888,7 @@ struct TfRowsBT {
     static constexpr int B = BB;
     static constexpr int MP = 1;
     static constexpr bool PIVOT = false;
+    static constexpr bool MASKED = false;          // (stored dense: tf_coop_hip.h shares these planes)
     const TfLevelArgs& a;
     int pg, e, p, len, start;
     TF_DEVICE_M TfRowsBT(const TfLevelArgs& a_, int pg_) : a(a_), pg(pg_) {
@@ -868,6 +921,11 @@ struct TfRowsBT {
         decode(i, raw, row);
     }
 };
+
+// entry (r, k) of a factor block of `Rows` is kept in memory / in the exchange slots; the others are
+// exact zeros that are never stored and read as a literal 0.0
+template <class Rows>
+TF_DEVICE_M constexpr bool tf_kept(int r, int k) { return !Rows::MASKED || TfMask<Rows::B>::nz(r, k); }
 
 // Rows requested ahead of their use in the level-1 walks: one (0) or two (1).  Two rows hide more
 // latency but cost 2 x (nnz + nvar) registers in kernels that already overflow into AGPRs; with the
@@ -1282,7 +1340,8 @@ TF_DEVICE void tfk_chunk_body(const TfLevelArgs& a, int pg, double* ylds = nullp
 #pragma unroll
                 for (int r = 0; r < B; ++r)
 #pragma unroll
-                    for (int k = 0; k < B; ++k) slot[(r * B + k) * 64] = Dinv[r][k];
+                    for (int k = 0; k < B; ++k)
+                        if (tf_kept<Rows>(r, k)) slot[(r * B + k) * 64] = Dinv[r][k];
             }
         }
         if (!PIV) fetch(MP, j + MP);
@@ -1294,7 +1353,8 @@ TF_DEVICE void tfk_chunk_body(const TfLevelArgs& a, int pg, double* ylds = nullp
 #pragma unroll
                 for (int r = 0; r < B; ++r)
 #pragma unroll
-                    for (int k = 0; k < B; ++k) slot[((q * B + r) * B + k) * 64] = R[q][0][r][k];
+                    for (int k = 0; k < B; ++k)
+                        if (tf_kept<Rows>(r, k)) slot[((q * B + r) * B + k) * 64] = R[q][0][r][k];
             TF_WG_BARRIER();
         }
 #pragma unroll
@@ -1320,6 +1380,7 @@ TF_DEVICE void tfk_chunk_body(const TfLevelArgs& a, int pg, double* ylds = nullp
                     for (int r = 0; r < B; ++r)
 #pragma unroll
                         for (int k = 0; k < B; ++k) {
+                            if (!tf_kept<Rows>(r, k)) continue;
                             tf_stp(a.Ut, (c * B + r) * B + k, L.plane, off, Un[c][r][k]);
                             if (ES && keep && c < MP)
                                 tf_stp(a.Et, (c * B + r) * B + k, L.plane, off, En[ES && c < MP ? c : 0][r][k]);
@@ -1390,7 +1451,8 @@ TF_DEVICE void tfk_chunk_body(const TfLevelArgs& a, int pg, double* ylds = nullp
 #pragma unroll
             for (int r = 0; r < B; ++r)
 #pragma unroll
-                for (int c = 0; c < B; ++c) hand[((k * B + r) * B + c) * 64] = Uh[k][0][r][c];
+                for (int c = 0; c < B; ++c)
+                    if (tf_kept<Rows>(r, c)) hand[((k * B + r) * B + c) * 64] = Uh[k][0][r][c];
         TF_WG_BARRIER();
         TF_WG_BARRIER();
     }
@@ -1453,7 +1515,7 @@ TF_DEVICE void tfk_rhs_follow_body(const TfLevelArgs& a, int pg, double* xch, do
 #pragma unroll
         for (int r = 0; r < B; ++r)
 #pragma unroll
-            for (int k = 0; k < B; ++k) Dinv[r][k] = slot[(r * B + k) * 64];
+            for (int k = 0; k < B; ++k) Dinv[r][k] = tf_kept<Rows>(r, k) ? slot[(r * B + k) * 64] : 0.0;
         tf_mv<B>(yn, Dinv, y[0]);
 #pragma unroll
         for (int t = 0; t < MP; ++t) tf_mm<B>(En[t], Dinv, Es[0][t]);
@@ -1468,7 +1530,7 @@ TF_DEVICE void tfk_rhs_follow_body(const TfLevelArgs& a, int pg, double* xch, do
 #pragma unroll
             for (int r = 0; r < B; ++r)
 #pragma unroll
-                for (int k = 0; k < B; ++k) M[r][k] = slot[((q * B + r) * B + k) * 64];
+                for (int k = 0; k < B; ++k) M[r][k] = tf_kept<Rows>(r, k) ? slot[((q * B + r) * B + k) * 64] : 0.0;
             tf_mv_sub<B>(y[q], M, yn);
 #pragma unroll
             for (int t = 0; t < MP; ++t) tf_mm_sub<B>(Es[q][t], M, En[t]);
@@ -1483,7 +1545,8 @@ TF_DEVICE void tfk_rhs_follow_body(const TfLevelArgs& a, int pg, double* xch, do
 #pragma unroll
                     for (int r = 0; r < B; ++r)
 #pragma unroll
-                        for (int k = 0; k < B; ++k) tf_stp(a.Et, (c * B + r) * B + k, L.plane, off, En[c][r][k]);
+                        for (int k = 0; k < B; ++k)
+                            if (tf_kept<Rows>(r, k)) tf_stp(a.Et, (c * B + r) * B + k, L.plane, off, En[c][r][k]);
             }
             if (STORE_Y) {
 #pragma unroll
@@ -1524,7 +1587,7 @@ TF_DEVICE void tfk_rhs_follow_body(const TfLevelArgs& a, int pg, double* xch, do
 #pragma unroll
         for (int r = 0; r < B; ++r)
 #pragma unroll
-            for (int c = 0; c < B; ++c) Uh[k][0][r][c] = hand[((k * B + r) * B + c) * 64];
+            for (int c = 0; c < B; ++c) Uh[k][0][r][c] = tf_kept<Rows>(r, c) ? hand[((k * B + r) * B + c) * 64] : 0.0;
     TF_WG_BARRIER();
     if (DIR > 0) TF_STAMP_T(a, 33, 64);
     tf_tips_out<Rows, DIR, true, true, false, true>(a, rows, pg, Uh, yh, Eh, asm_stage, nullptr);
@@ -1818,8 +1881,9 @@ TF_DEVICE void tfk_backsub_body(const TfLevelArgs& a, int pg) {
             for (int r = 0; r < B; ++r)
 #pragma unroll
                 for (int k = 0; k < B; ++k) {
-                    n.U[c][r][k] = tf_ldp(a.Ut, (c * B + r) * B + k, L.plane, off);
-                    if (WITH_E && c < MP) n.E[WITH_E && c < MP ? c : 0][r][k] = tf_ldp(a.Et, (c * B + r) * B + k, L.plane, off);
+                    const bool kept = tf_kept<Rows>(r, k);
+                    n.U[c][r][k] = kept ? tf_ldp(a.Ut, (c * B + r) * B + k, L.plane, off) : 0.0;
+                    if (WITH_E && c < MP) n.E[WITH_E && c < MP ? c : 0][r][k] = kept ? tf_ldp(a.Et, (c * B + r) * B + k, L.plane, off) : 0.0;
                 }
     };
     // TF_BACKSUB_DEPTH nodes of factors in flight per thread: the walk is a chain of loads
@@ -1932,7 +1996,8 @@ TF_DEVICE void tfk_backsub_twist_body(const TfLevelArgs& a, int pg, int dir,
 #pragma unroll
             for (int r = 0; r < B; ++r)
 #pragma unroll
-                for (int k = 0; k < B; ++k) U[c][r][k] = tf_ldp(a.Ut, (c * B + r) * B + k, L.plane, off);
+                for (int k = 0; k < B; ++k)
+                    U[c][r][k] = tf_kept<Rows>(r, k) ? tf_ldp(a.Ut, (c * B + r) * B + k, L.plane, off) : 0.0;
     };
     // a.upd_n (the launch that holds the re-elimination, YLDS): the solve is the last one of a time
     // step and what leaves is the new state, base + c0 x (one term) or base + (c0 k0 + c1 x) -- the

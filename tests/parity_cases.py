@@ -490,26 +490,35 @@ def check_adaptive_landing_reuse(backend):
         # The first trial of the next call queued ahead of the read of this call's error estimate
         # (ROW_general.QUEUE_NEXT_TRIAL): the same steps, earlier -- bit for bit the states of the
         # controller that launches every trial when it needs it, also when the caller changes dt, hands
-        # in a copy of the container, or other parameters (the queued step is dropped)
+        # in a copy of the container, or other parameters (the queued step is dropped: the call after
+        # each of these launches its own trial).  The states are read through a copy, which leaves the
+        # container on the device (f.uflat would detach it, and no call would ever take a queued step):
+        # tests/controller_cases.py has the helpers and the rest of the cases
+        from tests.controller_cases import snapshot, tally
         name, fd, pars, dt, _ = corpus.config_inputs(3, 400)
         m = device_model(name, backend)
-        out = []
+        out, hits = [], []
         for queue in (True, False):
             scheme = schemes.RODASPR(m, tol=1e-1)
             scheme.QUEUE_NEXT_TRIAL = queue
             f, t, p = m.fields_template(**fd), 0.3, pars
             states = []
-            with np.errstate(all="ignore"):
+            with tally() as rec, np.errstate(all="ignore"):
                 for k in range(22):
                     if k == 14:
                         f = f.copy()                     # another container: nothing queued applies
                     if k == 17:
                         p = dict(p, We=0.02)             # other parameters
                     t, f = scheme(t, f, dt if k < 10 or k >= 12 else 0.5 * dt, p)
-                    states.append(f.uflat.copy())
+                    states.append(snapshot(f))
             out.append(states)
+            hits.append(rec.hits(scheme))
         for a, b in zip(*out):
             assert np.isfinite(a).all() and np.array_equal(a, b)
+        # calls 0 and 1 start the controller up; 10 and 12 follow a change of dt (11 repeats 10's dt)
+        assert sum(hits[0]) >= 15 and sum(hits[1]) == 0, hits
+        assert [hits[0][k] for k in (10, 12, 14, 17)] == [0, 0, 0, 0], hits[0]
+        assert [hits[0][k] for k in (9, 11, 13, 16, 18)] == [1, 1, 1, 1, 1], hits[0]
     finally:
         _capi.DeviceSolver.step_row, _capi.DeviceSolver.step_row_queued = orig, orig_q
     # Simulation -> Theta on the constant-matrix model: one factorisation serves every landing step

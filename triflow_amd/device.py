@@ -111,6 +111,7 @@ class Stepper:
         self._bound_pars = None
         self._bound_x = None
         self._dirichlet = None
+        self._queued_owner = {}       # estimate mailbox -> (token of the step queued into it last, its scheme)
 
     # ---- slots ------------------------------------------------------------------
     def _live_users(self, slot):
@@ -190,15 +191,40 @@ class Stepper:
         fields._fill_from_device(self.compiled.model._dep_vars, arr[:, 0, :])
 
     # ---- inputs ------------------------------------------------------------------
+    def _input_keys(self, x, values):
+        """Value snapshots of the parameters (None: per-node values, which are not compared) and of
+        the grid."""
+        xkey = (x.size, float(x[0]), float(x[-1]))
+        mask = self.solver.model.spec["parvec_mask"]
+        scalar = all(np.ndim(v) == 0 or np.size(v) == 1 for v in values)
+        pkey = tuple(float(np.ravel(v)[0]) for v in values) if scalar and not mask else None
+        return pkey, xkey
+
+    def input_key(self, fields, pars):
+        """What a step from ``fields`` with ``pars`` would bind, by value: equal keys, same device
+        inputs.  None when that cannot be told without looking at arrays (per-node parameters, help
+        functions): such a step is never "the same" as an earlier one.  (On the host path of every
+        call that takes a queued step: plain floats are not put through NumPy.)"""
+        cm = self.compiled
+        if cm.nh != 0 or self.solver.model.spec["parvec_mask"]:
+            return None
+        pkey = []
+        for k in cm.pars:
+            v = pars[k]
+            if type(v) is not float:
+                if np.ndim(v) != 0 and np.size(v) != 1:
+                    return None
+                v = float(np.ravel(v)[0])
+            pkey.append(v)
+        x = fields["x"]
+        return tuple(pkey), (x.size, float(x[0]), float(x[-1]))
+
     def bind(self, fields, pars):
         """dx / x / parameters / help functions -> device (skipped when unchanged)."""
         cm = self.compiled
         x = np.asarray(fields["x"])
-        xkey = (x.size, float(x[0]), float(x[-1]))
         values = [pars[k] for k in cm.pars]        # KeyError for a missing parameter
-        mask = self.solver.model.spec["parvec_mask"]
-        scalar = all(np.ndim(v) == 0 or np.size(v) == 1 for v in values)
-        pkey = tuple(float(np.ravel(v)[0]) for v in values) if scalar and not mask else None
+        pkey, xkey = self._input_keys(x, values)
         helper_free = cm.nh == 0
         if helper_free and pkey is not None and pkey == self._bound_pars and xkey == self._bound_x:
             return

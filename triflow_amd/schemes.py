@@ -87,6 +87,14 @@ def _difference_norms(a, b, ord):
             for key in b.dependent_variables]
 
 
+def _backing_key(fields):
+    """``(stepper, slot, version)`` of a container whose state is resident and current, else None."""
+    backing = getattr(fields, "_device_backing", lambda: None)()
+    if backing is None or not backing.valid():
+        return None
+    return backing.stepper, backing.slot, backing.version
+
+
 #: A whole trial of the step-doubling controller as one library call (``tf_step_doubling``).  Off by
 #: default since round 3: the launches are asynchronous either way and the GPU is the bottleneck, so
 #: the fused call has never been faster than the loop below (config 2, N = 1e6: 0.670 against 0.657 ms
@@ -270,7 +278,11 @@ class ROW_general:
     #: state of a smooth run the next thing it will be asked for is known: the same step from the state
     #: this trial produced (the next call's first trial, ``dt`` the caller's).  That step is queued
     #: *before* the estimate is read (``tf_step_row_queued``), and the next call takes it if it asks for
-    #: exactly that (same container, ``t``, ``dt``, parameters, hook); otherwise it is dropped.  Nothing
+    #: exactly that (``_is_queued_step``): the same container object, still in the state slot (slot and
+    #: version) it had and with no node assigned since; ``t`` and ``dt`` equal to the bit; parameters and grid equal *by value* (scalar parameters, no help functions -- otherwise
+    #: never); the queued step's result still in its slot; its estimate still the last one posted to its
+    #: mailbox (another scheme on the same solver may have posted since); no hook.  Otherwise it is
+    #: dropped and the call launches its own trial, which binds and acquires as ever.  Nothing
     #: is returned unverified: every trial's estimate is read before the controller acts on it, in the
     #: reference's order (profiles/r04_default_user_path.txt: 682 -> see there, accepted dt/s).
     QUEUE_NEXT_TRIAL = True
@@ -285,26 +297,73 @@ class ROW_general:
                   and getattr(fields, "_device_backing", lambda: None)() is not None)
         if not usable:
             return self._fixed_step(t, fields, dt, pars, hook)
-        # (dt "the same": a driver that lands on t + dt asks for target - t, the last call's dt give or
-        # take the rounding of the sum -- the tolerance of the landing step, REUSE_TRIAL_AS_LANDING)
-        if spec is not None and spec["fields"] is fields and spec["t"] == t and spec["pars"] is pars \
-                and abs(spec["dt"] - dt) <= np.spacing(abs(t + dt)):
+        # (dt the same to the bit: a driver that lands on t + dt asks for target - t, the last call's dt give
+        # or take the rounding of the sum.  While t stays in one binade that is one and the same number,
+        # and at the crossing the queued step is dropped: taking it would be the landing step's
+        # tolerance, REUSE_TRIAL_AS_LANDING, not the bits of the controller that queues nothing)
+        stepper = stepper_for(self._model, fields, pars)
+        inputs = stepper.input_key(fields, pars)     # (the containers of a run share their coordinates)
+        if spec is not None and self._is_queued_step(spec, t, fields, dt, inputs):
             new_t, new_fields, fetch, slot = t + dt, spec["new_fields"], spec["fetch"], spec["slot"]
         else:
-            slot = 1
+            slot, _ = self._mailbox(stepper)
             new_t, new_fields, fetch = self._fixed_step(t, fields, dt, pars, hook, err_slot=slot)
         # the trial that would follow if this one is accepted and lands on the target with the
         # controller's step still above the caller's dt: queued now, looked at by the next call
         if new_t >= target and dt == getattr(self, "_call_dt", None) \
                 and abs((target - t) - dt) <= np.spacing(abs(target)):
-            nslot = 2 if slot == 1 else 1
+            nslot, token = self._mailbox(stepper, avoid=(slot,))
             nt, nf, nfetch = self._fixed_step(target, new_fields, dt, pars, hook, err_slot=nslot)
-            self._spec = dict(fields=new_fields, t=target, dt=dt, pars=pars, new_t=nt, new_fields=nf,
-                              fetch=nfetch, slot=nslot)
+            src, dst = _backing_key(new_fields), _backing_key(nf)
+            if src is not None and dst is not None and src[0] is stepper:
+                self._spec = dict(fields=new_fields, t=target, dt=dt, src=src, dst=dst, inputs=inputs,
+                                  new_t=nt, new_fields=nf, fetch=nfetch, slot=nslot, token=token)
         err = fetch()
         if err > self._tol:
             self._spec = None              # rejected: what was queued behind it started from a state nobody keeps
         return new_t, new_fields, err
+
+    def _mailbox(self, stepper, avoid=()):
+        """Estimate mailbox (1 ... 3) for a step about to be queued.  Every scheme on a solver posts into
+        the same three, and a post replaces an estimate nobody has read yet: one that holds the estimate
+        of a step some scheme still has queued ahead is passed over while another is free (two schemes
+        called in turn keep their queued steps), and the mailbox records whose estimate it holds last, so
+        that a step whose estimate was replaced after all is not taken (``_is_queued_step``)."""
+        owners = stepper._queued_owner
+        first = None
+        for slot in (1, 2, 3):
+            if slot in avoid:
+                continue
+            if first is None:
+                first = slot
+            owner = owners.get(slot)
+            if owner is not None:
+                spec = getattr(owner[1](), "_spec", None)
+                if spec is not None and spec["token"] is owner[0]:
+                    continue                          # still waited for
+            break
+        else:
+            slot = first                              # all waited for: its owner finds the estimate replaced
+        token = object()
+        owners[slot] = (token, weakref.ref(self))
+        return slot, token
+
+    @staticmethod
+    def _is_queued_step(spec, t, fields, dt, inputs):
+        """Is the step asked for the one ``spec`` describes, and is what it left on the device still there?
+        The same container, in the state slot it was in and with nothing assigned to it since; ``t`` and
+        ``dt`` to the bit; the values of the parameters and the grid (``inputs``: ``Stepper.input_key``); the queued
+        step's own state slot; its estimate still the last one posted to its mailbox."""
+        if spec["fields"] is not fields or spec["t"] != t or spec["dt"] != dt:
+            return False
+        src, dst = _backing_key(fields), _backing_key(spec["new_fields"])
+        if src is None or src != spec["src"] or dst is None or dst != spec["dst"]:
+            return False
+        if fields._pending_point_writes():
+            return False
+        if src[0]._queued_owner.get(spec["slot"], (None,))[0] is not spec["token"]:
+            return False
+        return inputs is not None and spec["inputs"] == inputs
 
     def _landing_from_trial(self, new_fields, dt_used, t, target, pars, hook):
         if not self.REUSE_TRIAL_AS_LANDING or abs((target - t) - dt_used) > np.spacing(abs(target)):

@@ -10,7 +10,9 @@ operation tree (no re-association, no common-subexpression rewriting, no FMA
 contraction; the C compiler may only share bit-identical subtrees).  Name
 overrides follow the reference's module dictionary: ``Heaviside`` is
 identically one (``compilers.py:204-205``), ``Max``/``Min`` are
-``numpy.maximum``/``minimum`` chains.
+``numpy.maximum``/``minimum`` chains.  A model built with ``heaviside="exact"``
+opts out of the first: ``Heaviside`` is ``numpy.heaviside``, ``DiracDelta`` zero,
+``Piecewise`` ``numpy.select``.
 """
 
 import ast
@@ -33,6 +35,44 @@ class UnsupportedExpression(NotImplementedError):
     pass
 
 
+#: the two meanings of the discontinuous vocabulary (``Model(..., heaviside=...)``):
+#: "one" -- every Heaviside is the literal 1.0, as in the reference's module dictionary; DiracDelta and
+#: Piecewise are refused.  "exact" -- Heaviside is numpy.heaviside, DiracDelta is zero, Piecewise is
+#: numpy.select.
+HEAVISIDE_MODES = ("one", "exact")
+
+_EXACT_HINT = '; Model(..., heaviside="exact") lowers Heaviside, DiracDelta and Piecewise exactly'
+
+
+def _dirac_zero(a, *_):
+    return np.zeros_like(a)
+
+
+#: what SymPy's lambdify is given for the names NumPy does not define, per mode: the printed call keeps
+#: the name, and this is its meaning
+LAMBDIFY_MODULES = {
+    "one": [{"Heaviside": lambda *a: 1}, "numpy"],
+    "exact": [{"Heaviside": np.heaviside, "DiracDelta": _dirac_zero}, "numpy"],
+}
+
+
+def validate_heaviside(mode):
+    """The one validator of the setting (Model, hip_compiler and the lowering all come here)."""
+    if mode not in HEAVISIDE_MODES:
+        raise ValueError("heaviside=%r: expected one of %s" % (mode, ", ".join(map(repr, HEAVISIDE_MODES))))
+    return mode
+
+
+def heaviside_mode(model):
+    """The one place the lowering reads the mode from: the model's ``_heaviside`` (a foreign model
+    without the attribute is in the default mode; ``hip_compiler(model, heaviside=...)`` sets it)."""
+    return validate_heaviside(getattr(model, "_heaviside", "one"))
+
+
+_COMPARE = {"greater": ">", "greater_equal": ">=", "less": "<", "less_equal": "<=", "equal": "==",
+            "not_equal": "!="}
+
+
 def _dbl(value):
     """C literal with the exact binary value of a Python number."""
     f = float(value)
@@ -50,8 +90,9 @@ class _CEmitter(ast.NodeVisitor):
     use the exact reciprocal form ``tf_div_u`` with the divisor and its
     reciprocal hoisted out of the node loop."""
 
-    def __init__(self, names, uniform_names=()):
+    def __init__(self, names, uniform_names=(), heaviside="one"):
         self.names = names          # python identifier -> C expression
+        self.exact = heaviside == "exact"
         self.uniform_names = set(uniform_names)
         self.denominators = {}      # C expression -> index
         self.den_count = {}         # C expression -> number of quotients using it
@@ -117,7 +158,11 @@ class _CEmitter(ast.NodeVisitor):
             # one true division for the reciprocal, then the exact 3-op quotient
             if self.is_uniform(node.right) or self.shared.get(den, 0) >= 2:
                 k = self.denominators.setdefault(den, len(self.denominators))
-                return "tf_div_u(%s, tf_den%d, tf_rden%d)" % (self.visit(node.left), k, k)
+                # (exact mode: its states may be infinite where a step function keeps them out of the
+                # result, and a tie of Max(U, 0) is a zero numerator whose sign counts; tf_div_x is
+                # tf_div_u with IEEE's quotient for a non-finite or zero numerator)
+                return "%s(%s, tf_den%d, tf_rden%d)" % ("tf_div_x" if self.exact else "tf_div_u",
+                                                        self.visit(node.left), k, k)
         ops = {ast.Add: "+", ast.Sub: "-", ast.Mult: "*", ast.Div: "/"}
         for klass, sym in ops.items():
             if isinstance(node.op, klass):
@@ -151,7 +196,24 @@ class _CEmitter(ast.NodeVisitor):
     def visit_Call(self, node):
         name = node.func.attr if isinstance(node.func, ast.Attribute) else node.func.id
         if name == "Heaviside":
-            return "1.0"                           # reference compilers.py:204-205
+            if not self.exact:
+                return "1.0"                       # reference compilers.py:204-205
+            if len(node.args) not in (1, 2) or node.keywords:
+                raise UnsupportedExpression("Heaviside with %d arguments" % len(node.args))
+            # SymPy prints the value at zero; a one-argument call (older SymPy) means 1/2
+            h0 = self.visit(node.args[1]) if len(node.args) == 2 else "0.5"
+            return "tf_heaviside(%s, %s)" % (self.visit(node.args[0]), h0)
+        if name == "DiracDelta" and self.exact:
+            # only ever the derivative of a Heaviside of the state: the mass at the kink is dropped, as
+            # SymPy drops it when it differentiates a Piecewise (the arguments are still checked)
+            for a in node.args:
+                self.visit(a)
+            return "0.0"
+        if name == "select" and self.exact:
+            return self._select(node)
+        if name == "reduce" and isinstance(node.func, ast.Attribute) and isinstance(node.func.value, ast.Name) \
+                and node.func.value.id in ("logical_and", "logical_or"):
+            name = node.func.value.id               # (refused below, as greater / less ... are)
         if name == "reduce":                       # reduce(maximum, [a, b, ...])
             op = node.args[0]
             opname = op.attr if isinstance(op, ast.Attribute) else op.id
@@ -178,17 +240,59 @@ class _CEmitter(ast.NodeVisitor):
                     and name not in ("abs", "absolute", "fabs", "sign", "floor", "ceil", "sqrt"):
                 return self.host_const(node)
             return "%s(%s)" % (_FUNCS_1[name], self.visit(node.args[0]))
-        raise UnsupportedExpression("function %r is not supported by the HIP compiler" % name)
+        if self.exact and (name in _COMPARE or name in ("logical_not", "logical_and", "logical_or")):
+            raise UnsupportedExpression("function %r is only supported as a condition of Piecewise, not as a value"
+                                        % name)
+        hint = _EXACT_HINT if not self.exact and name in ("select", "DiracDelta") else ""
+        raise UnsupportedExpression("function %r is not supported by the HIP compiler%s" % (name, hint))
+
+    def _select(self, node):
+        """``select([c1, c2, ...], [v1, v2, ...], default=nan)``, SymPy's print of a Piecewise: the first
+        true condition wins, the default if none is.  A chain of tf_select, whose arguments are all
+        evaluated, as NumPy evaluates every branch: the value is one of theirs, bit for bit."""
+        if len(node.args) != 2 or not all(isinstance(a, (ast.List, ast.Tuple)) for a in node.args) \
+                or len(node.args[0].elts) != len(node.args[1].elts) or not node.args[0].elts \
+                or [k.arg for k in node.keywords] not in ([], ["default"]):
+            raise UnsupportedExpression("unexpected form of select: " + ast.unparse(node))
+        out = "tf_nan()"
+        if node.keywords:
+            d = node.keywords[0].value
+            out = "tf_nan()" if isinstance(d, ast.Name) and d.id == "nan" else self.visit(d)
+        for cond, value in reversed(list(zip(node.args[0].elts, node.args[1].elts))):
+            out = "tf_select(%s, %s, %s)" % (self._cond(cond), self.visit(value), out)
+        return out
+
+    def _cond(self, node):
+        """A condition of a Piecewise, as the NumPy printer writes Gt, Ge, Lt, Le, Eq, Ne, And, Or, Not and
+        the literals -> a C bool with the same IEEE meaning (every comparison with a NaN is false,
+        ``!=`` is true)."""
+        if isinstance(node, ast.Constant) and isinstance(node.value, bool):
+            return "true" if node.value else "false"
+        if isinstance(node, ast.Call) and not node.keywords:
+            f = node.func
+            name = f.attr if isinstance(f, ast.Attribute) else getattr(f, "id", None)
+            if name in _COMPARE and len(node.args) == 2:
+                return "(%s %s %s)" % (self.visit(node.args[0]), _COMPARE[name], self.visit(node.args[1]))
+            if name == "logical_not" and len(node.args) == 1:
+                return "(!%s)" % self._cond(node.args[0])
+            if name == "reduce" and isinstance(f, ast.Attribute) and isinstance(f.value, ast.Name) \
+                    and f.value.id in ("logical_and", "logical_or") and len(node.args) == 1 \
+                    and isinstance(node.args[0], (ast.List, ast.Tuple)) and node.args[0].elts:
+                # (& and | of bools, not && and ||: nothing to short-circuit, so nothing to branch on)
+                op = " & " if f.value.id == "logical_and" else " | "
+                return "(%s)" % op.join(self._cond(e) for e in node.args[0].elts)
+        raise UnsupportedExpression("condition %r of a Piecewise is not supported by the HIP compiler"
+                                    % ast.unparse(node))
 
     def generic_visit(self, node):
         raise UnsupportedExpression(ast.dump(node))
 
 
-def _printed_expressions(symbolic_args, exprs):
+def _printed_expressions(symbolic_args, exprs, heaviside="one"):
     """The element expressions of the list SymPy's lambdify would evaluate."""
     if not exprs:
         return []
-    func = lambdify(symbolic_args, exprs, modules=[{"Heaviside": lambda *a: 1}, "numpy"],
+    func = lambdify(symbolic_args, exprs, modules=LAMBDIFY_MODULES[heaviside],
                     cse=False)
     src = inspect.getsource(func)
     tree = ast.parse(src)
@@ -273,16 +377,17 @@ def lower_model(model, parvec_mask=0, seg=8, sweep_block=64):
     pat_var = [(k // nvar) % nvar for k in sparse]
     pat_off = [(k // nvar) // nvar - real_mp for k in sparse]
 
+    mode = heaviside_mode(model)
     names, decls, uniform = _stencil_names(fields, pars, mp, parvec_mask)
-    f_nodes = _printed_expressions(model._symbolic_args, model.F_array.tolist())
-    j_nodes = _printed_expressions(model._symbolic_args, model._J_sparse_array.tolist())
+    f_nodes = _printed_expressions(model._symbolic_args, model.F_array.tolist(), mode)
+    j_nodes = _printed_expressions(model._symbolic_args, model._J_sparse_array.tolist(), mode)
     host_consts = {}
 
     def emit_all(nodes):
-        first = _CEmitter(names, uniform)           # pass 1: count divisor reuse
+        first = _CEmitter(names, uniform, mode)     # pass 1: count divisor reuse
         for n in nodes:
             first.visit(n)
-        second = _CEmitter(names, uniform)
+        second = _CEmitter(names, uniform, mode)
         second.shared = first.den_count
         second.host_consts = host_consts            # one table for F and J
         return second, [second.visit(n) for n in nodes]
@@ -297,7 +402,7 @@ def lower_model(model, parvec_mask=0, seg=8, sweep_block=64):
     # thread instead of reading them back from the value table at every node
     j_uniform = [1 if emit_j.is_uniform(n) else 0 for n in j_nodes]
 
-    j_alias, j_alias_scale = _proportional_entries(model, j_uniform)
+    j_alias, j_alias_scale = _proportional_entries(model, j_uniform, mode)
 
     def body(outname, exprs, emitter, only=None):
         lines = ["    " + d for d in decls if only is None or d.split("=")[1].strip().startswith("par[")]
@@ -325,6 +430,8 @@ def lower_model(model, parvec_mask=0, seg=8, sweep_block=64):
     src = "\n".join([
         "// generated by triflow_amd.codegen -- do not edit",
         "// equations: " + " ; ".join(str(e) for e in model._diff_eqs),
+        *(["// heaviside: exact (Heaviside = numpy.heaviside, DiracDelta = 0, Piecewise = numpy.select)"]
+          if mode == "exact" else []),
         "#define TF_NVAR %d" % nvar,
         "#define TF_NH %d" % nh,
         "#define TF_MP %d" % mp,
@@ -360,7 +467,7 @@ def lower_model(model, parvec_mask=0, seg=8, sweep_block=64):
                 sweep_block=sweep_block, uses_x=int(uses_x), parvec_mask=int(parvec_mask),
                 b2=mp * nvar, pat_eq=pat_eq, pat_var=pat_var, pat_off=pat_off, j_uniform=j_uniform,
                 j_alias=j_alias, j_alias_scale=j_alias_scale,
-                blk_nz=blk_nz, fields=fields, pars=pars)
+                blk_nz=blk_nz, fields=fields, pars=pars, heaviside=mode)
     return src, spec
 
 
@@ -372,26 +479,28 @@ def _lower_node_expressions(model, exprs, parvec_mask):
     """What the probes and the recorders share: discretised SymPy expressions over the model's symbolic
     arguments, printed by the same lambdify call as F and emitted by the same ``_CEmitter``.  Returns
     the lines that open the per-node body (the window / parameter names, the hoisted divisors), the C
-    expressions, the uniform powers / libm calls evaluated on the host, whether ``x`` is read, and the
-    model's parameter names."""
+    expressions, the uniform powers / libm calls evaluated on the host, whether ``x`` is read, the
+    model's parameter names and its mode of Heaviside / DiracDelta / Piecewise."""
     fields = list(model._dep_vars) + list(model._help_funcs)
     pars = list(model._pars)
     mp = max((model._window_range - 1) // 2, 1)
     names, decls, uniform = _stencil_names(fields, pars, mp, parvec_mask)
     import sympy
+    mode = heaviside_mode(model)
     for e in exprs:
-        # In F and J, Heaviside is identically one (the reference's module dictionary: it only ever
-        # stands there as the derivative of Max / Min).  An observer is not differentiated: a Heaviside
-        # in it is the user's own, and a step function that is one everywhere is not what they wrote.
-        if sympy.sympify(e).has(sympy.Heaviside):
+        # In the default mode Heaviside is identically one in F and J (the reference's module dictionary:
+        # it only ever stands there as the derivative of Max / Min).  An observer is not differentiated: a
+        # Heaviside in it is the user's own, and a step function that is one everywhere is not what they
+        # wrote.  (In the exact mode it is what they wrote.)
+        if mode == "one" and sympy.sympify(e).has(sympy.Heaviside):
             raise UnsupportedExpression("function 'Heaviside' is not supported in a probe or recorder: the HIP "
                                         "compiler takes it as identically one, as the reference does in J; "
-                                        "write the step with Max / Min / sign")
-    nodes = _printed_expressions(model._symbolic_args, list(exprs))
-    first = _CEmitter(names, uniform)               # pass 1: count divisor reuse
+                                        "write the step with Max / Min / sign" + _EXACT_HINT)
+    nodes = _printed_expressions(model._symbolic_args, list(exprs), mode)
+    first = _CEmitter(names, uniform, mode)         # pass 1: count divisor reuse
     for n in nodes:
         first.visit(n)
-    emit = _CEmitter(names, uniform)
+    emit = _CEmitter(names, uniform, mode)
     emit.shared = first.den_count
     out = [emit.visit(n) for n in nodes]
     hc_list = [src_ for src_, _ in sorted(emit.host_consts.items(), key=lambda kv: kv[1])]
@@ -401,7 +510,7 @@ def _lower_node_expressions(model, exprs, parvec_mask):
     for den, k in sorted(emit.denominators.items(), key=lambda kv: kv[1]):
         lines += ["    const double tf_den%d = %s;" % (k, den),
                   "    const double tf_rden%d = 1.0 / tf_den%d;" % (k, k)]
-    return lines, out, hc_list, uses_x, pars
+    return lines, out, hc_list, uses_x, pars, mode
 
 
 def lower_probes(model, exprs, reductions, parvec_mask=0):
@@ -413,7 +522,7 @@ def lower_probes(model, exprs, reductions, parvec_mask=0):
     Uniform powers / libm calls become host constants of the probes (``spec["host_consts"]``, the
     probe's own argument buffer: the model's parameter slots are not touched)."""
     kinds = [PROBE_REDUCTIONS.index(r) for r in reductions]
-    lines, out, hc_list, uses_x, pars = _lower_node_expressions(model, exprs, parvec_mask)
+    lines, out, hc_list, uses_x, pars, mode = _lower_node_expressions(model, exprs, parvec_mask)
     lines += ["    P[%d] = %s;" % (i, c) for i, c in enumerate(out)]
     block = "\n".join([
         "// device probes, generated by triflow_amd.codegen.lower_probes -- do not edit",
@@ -428,7 +537,8 @@ def lower_probes(model, exprs, reductions, parvec_mask=0):
         "\n".join(lines),
         "}",
         ""])
-    spec = dict(nprobe=len(out), kinds=kinds, host_consts=hc_list, pars=pars, uses_x=int(uses_x))
+    spec = dict(nprobe=len(out), kinds=kinds, host_consts=hc_list, pars=pars, uses_x=int(uses_x),
+                heaviside=mode)
     return block, spec
 
 
@@ -442,7 +552,7 @@ def lower_records(model, exprs, parvec_mask=0):
     and the constants the runtime needs.  Lowered as the probes are (``_lower_node_expressions``): the
     per-node values are the bits NumPy computes from the printed expressions; the host constants go
     into the recorders' own argument buffer (``spec["host_consts"]``)."""
-    lines, out, hc_list, uses_x, pars = _lower_node_expressions(model, exprs, parvec_mask)
+    lines, out, hc_list, uses_x, pars, mode = _lower_node_expressions(model, exprs, parvec_mask)
     lines += ["    switch (k) {"]
     lines += ["    case %d: return %s;" % (i, c) for i, c in enumerate(out)]
     lines += ["    default: return 0.0;", "    }"]
@@ -457,7 +567,8 @@ def lower_records(model, exprs, parvec_mask=0):
         "\n".join(lines),
         "}",
         ""])
-    spec = dict(nrec=len(out), host_consts=hc_list, pars=pars, uses_x=int(uses_x))
+    spec = dict(nrec=len(out), host_consts=hc_list, pars=pars, uses_x=int(uses_x),
+                heaviside=mode)
     return block, spec
 
 
@@ -467,7 +578,7 @@ def lower_statistics(model, exprs, parvec_mask=0):
     the constants the runtime needs.  Lowered as the probes and the recorders are
     (``_lower_node_expressions``): the per-node values are the bits NumPy computes from the printed
     expressions; the host constants go into the statistics' own argument buffer (``spec["host_consts"]``)."""
-    lines, out, hc_list, uses_x, pars = _lower_node_expressions(model, exprs, parvec_mask)
+    lines, out, hc_list, uses_x, pars, mode = _lower_node_expressions(model, exprs, parvec_mask)
     lines += ["    switch (k) {"]
     lines += ["    case %d: return %s;" % (i, c) for i, c in enumerate(out)]
     lines += ["    default: return 0.0;", "    }"]
@@ -482,7 +593,8 @@ def lower_statistics(model, exprs, parvec_mask=0):
         "\n".join(lines),
         "}",
         ""])
-    spec = dict(nstat=len(out), host_consts=hc_list, pars=pars, uses_x=int(uses_x))
+    spec = dict(nstat=len(out), host_consts=hc_list, pars=pars, uses_x=int(uses_x),
+                heaviside=mode)
     return block, spec
 
 
@@ -493,7 +605,7 @@ def lower_spectra(model, exprs, parvec_mask=0):
     the per-node values are the bits NumPy computes from the printed expressions; the host constants go
     into the spectra's own argument buffer (``spec["host_consts"]``).  The modes are not part of the
     block: spectra of the same expressions share a code object whatever their modes."""
-    lines, out, hc_list, uses_x, pars = _lower_node_expressions(model, exprs, parvec_mask)
+    lines, out, hc_list, uses_x, pars, mode = _lower_node_expressions(model, exprs, parvec_mask)
     lines += ["    switch (k) {"]
     lines += ["    case %d: return %s;" % (i, c) for i, c in enumerate(out)]
     lines += ["    default: return 0.0;", "    }"]
@@ -508,7 +620,8 @@ def lower_spectra(model, exprs, parvec_mask=0):
         "\n".join(lines),
         "}",
         ""])
-    spec = dict(nspec=len(out), host_consts=hc_list, pars=pars, uses_x=int(uses_x))
+    spec = dict(nspec=len(out), host_consts=hc_list, pars=pars, uses_x=int(uses_x),
+                heaviside=mode)
     return block, spec
 
 
@@ -520,7 +633,7 @@ def lower_extrema(model, exprs, parvec_mask=0):
     into the extrema's own argument buffer (``spec["host_consts"]``).  Kind, threshold, ``max_count`` and
     ``every`` are not part of the block: they are launch arguments, and sets that differ only in them
     share a code object."""
-    lines, out, hc_list, uses_x, pars = _lower_node_expressions(model, exprs, parvec_mask)
+    lines, out, hc_list, uses_x, pars, mode = _lower_node_expressions(model, exprs, parvec_mask)
     lines += ["    switch (k) {"]
     lines += ["    case %d: return %s;" % (i, c) for i, c in enumerate(out)]
     lines += ["    default: return 0.0;", "    }"]
@@ -535,11 +648,12 @@ def lower_extrema(model, exprs, parvec_mask=0):
         "\n".join(lines),
         "}",
         ""])
-    spec = dict(next=len(out), host_consts=hc_list, pars=pars, uses_x=int(uses_x))
+    spec = dict(next=len(out), host_consts=hc_list, pars=pars, uses_x=int(uses_x),
+                heaviside=mode)
     return block, spec
 
 
-def _proportional_entries(model, j_uniform):
+def _proportional_entries(model, j_uniform, heaviside="one"):
     """Jacobian entries that are an exact power-of-two multiple of an earlier node-dependent
     entry (``-q*dxT/h`` differentiated with respect to ``T_m1`` and ``T_p1``; ``We*h*dxxxh`` with
     respect to the four neighbours of ``h``; a reaction term that enters two equations with
@@ -548,14 +662,20 @@ def _proportional_entries(model, j_uniform):
     (i) SymPy proves the proportionality and (ii) the two expressions, evaluated the way the
     reference evaluates them (the lambdified NumPy code whose operation tree the C code repeats),
     agree *bit for bit* on random inputs -- scaling by a power of two commutes with every
-    rounding, a different association of the same product would not."""
+    rounding, a different association of the same product would not.  In the exact mode an entry with a
+    Heaviside, a DiracDelta or a Piecewise is never an alias and never the source of one: random samples
+    do not visit its kinks."""
     exprs = model._J_sparse_array.tolist()
     nnz = len(exprs)
     alias, scale = [-1] * nnz, [1.0] * nnz
     cand = [k for k in range(nnz) if not j_uniform[k]]
+    if heaviside == "exact":
+        import sympy
+        cand = [k for k in cand if not sympy.sympify(exprs[k]).has(sympy.Heaviside, sympy.DiracDelta,
+                                                                   sympy.Piecewise)]
     if len(cand) < 2:
         return alias, scale
-    func = lambdify(model._symbolic_args, exprs, modules=[{"Heaviside": lambda *a: 1}, "numpy"], cse=False)
+    func = lambdify(model._symbolic_args, exprs, modules=LAMBDIFY_MODULES[heaviside], cse=False)
     rng = np.random.default_rng(12345)
     samples = []
     for _ in range(2):
@@ -599,6 +719,12 @@ _HOST_NS = {name: getattr(np, name) for name in
             ("sqrt", "exp", "log", "sin", "cos", "tan", "tanh", "sinh", "cosh", "arctan", "arcsin",
              "arccos", "log10", "log2", "cbrt", "expm1", "log1p", "maximum", "minimum", "pi")}
 _HOST_NS["E"] = _HOST_NS["e"] = np.e
+# a uniform Heaviside / Piecewise inside a hoisted power or libm call: the meaning of its mode
+_HOST_NS_MODE = {
+    "one": {"Heaviside": lambda *a: np.float64(1.0)},
+    "exact": {"Heaviside": np.heaviside, "DiracDelta": _dirac_zero, "select": np.select, "nan": np.nan,
+              **{name: getattr(np, name) for name in (*_COMPARE, "logical_and", "logical_or", "logical_not")}},
+}
 
 
 def eval_host_constants(spec, dx, par_values):
@@ -609,7 +735,8 @@ def eval_host_constants(spec, dx, par_values):
     out = []
     for src_ in spec["host_consts"]:
         with np.errstate(all="ignore"):
-            out.append(float(eval(src_, {"__builtins__": {}, **_HOST_NS}, env)))
+            out.append(float(eval(src_, {"__builtins__": {}, **_HOST_NS,
+                                         **_HOST_NS_MODE[spec.get("heaviside", "one")]}, env)))
     return out
 
 

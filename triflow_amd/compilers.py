@@ -247,14 +247,21 @@ def _build_locked(model, source, tag, hsaco, observer=None):
                 pass
 
 
-def build_code_object(model, parvec_mask=0, seg=None, sweep_block=None):
-    """Model -> (path of the cached gfx950 code object, spec dict)."""
-    seg = seg or int(os.environ.get("TRIFLOW_SWEEP_SEG", "8"))
-    sweep_block = sweep_block or int(os.environ.get("TRIFLOW_SWEEP_BLOCK", "256"))
+def code_object_source(model, parvec_mask=0, seg=8, sweep_block=256):
+    """(translation unit, cache tag, spec) of a model's code object, without building it.  The mode of
+    Heaviside / DiracDelta / Piecewise (``model._heaviside``) is part of the source, so of the tag."""
     body, spec = codegen.lower_model(model, parvec_mask=parvec_mask, seg=seg,
                                      sweep_block=sweep_block)
     source = _TU_HEAD % "" + body + _TU_TAIL
     tag = codegen.source_hash(source, _skeleton_stamp(), " ".join(HIPCC_FLAGS), hipcc_version(), os.environ.get("TRIFLOW_SPILL_GATE", "kernel"), "elf")
+    return source, tag, spec
+
+
+def build_code_object(model, parvec_mask=0, seg=None, sweep_block=None):
+    """Model -> (path of the cached gfx950 code object, spec dict)."""
+    seg = seg or int(os.environ.get("TRIFLOW_SWEEP_SEG", "8"))
+    sweep_block = sweep_block or int(os.environ.get("TRIFLOW_SWEEP_BLOCK", "256"))
+    source, tag, spec = code_object_source(model, parvec_mask, seg, sweep_block)
     os.makedirs(CACHE_DIR, exist_ok=True)
     hsaco = os.path.join(CACHE_DIR, "model_%s.hsaco" % tag)
     _build_locked(model, source, tag, hsaco)
@@ -546,8 +553,20 @@ class CompiledModel:
         return pat.from_gathered(solver.get_J_mapped())
 
 
-def hip_compiler(model, backend=None):
-    """``compiler(model) -> (F_function, J_function)`` for the MI355X."""
+def hip_compiler(model, backend=None, heaviside=None):
+    """``compiler(model) -> (F_function, J_function)`` for the MI355X.  ``heaviside``: "one" or "exact",
+    the meaning of Heaviside / DiracDelta / Piecewise; ``None`` keeps the model's
+    own ``_heaviside`` (the default mode for a model without one).  A foreign model opts in with
+    ``partial(hip_compiler, heaviside="exact")``: the mode is then written to ``model._heaviside``,
+    the one place every lowering -- its observers' too -- reads it from.  A model that already has a
+    mode is not given another one behind its back (its observers were lowered in it): that is a
+    ``ValueError``."""
+    if heaviside is not None:
+        codegen.validate_heaviside(heaviside)
+        if getattr(model, "_heaviside", heaviside) != heaviside:
+            raise ValueError("heaviside=%r: the model was built with heaviside=%r"
+                             % (heaviside, model._heaviside))
+        model._heaviside = heaviside
     compiled = CompiledModel(model, backend)
 
     def F_function(*args):

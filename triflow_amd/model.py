@@ -26,6 +26,7 @@ from functools import partial
 import numpy as np
 import sympy as sp
 
+from .codegen import validate_heaviside
 from .fields import BaseFields
 from .routines import F_Routine, J_Routine
 
@@ -64,8 +65,9 @@ def _node_symbol(name, offset):
     return sp.Symbol("%s_%s%i" % (name, "m" if offset < 0 else "p", abs(offset)))
 
 
-def _rebuild_model(eqs, dep, pars, helps, bdcs, compiler):
-    return Model(eqs, dep, pars, helps, bdcs, compiler=compiler)
+def _rebuild_model(eqs, dep, pars, helps, bdcs, compiler, heaviside="one"):
+    # (the last argument is defaulted: pickles written before the keyword existed still load)
+    return Model(eqs, dep, pars, helps, bdcs, compiler=compiler, heaviside=heaviside)
 
 
 class Model:
@@ -78,12 +80,19 @@ class Model:
     string spellings ``"theano"`` and ``"numpy"`` resolve to here; any callable
     ``compiler(model) -> (F_function, J_function)`` is used as is (that is how
     the tests inject the CPU oracle).
+
+    ``heaviside`` is this package's own keyword: ``"one"`` (the default) takes every ``Heaviside`` as
+    identically one, as the reference's module dictionary does, and refuses ``DiracDelta`` and
+    ``Piecewise``; ``"exact"`` lowers ``Heaviside(a, h0)`` as ``numpy.heaviside``, ``DiracDelta`` as
+    zero and ``Piecewise`` as ``numpy.select``, in F, in J and in every observer of the model
+    (DESIGN.md section 20).
     """
 
     def __init__(self, differential_equations, dependent_variables,
                  parameters=None, help_functions=None, bdc_conditions=None,
                  compiler="hip", simplify=False, fdiff_jac=False, double=True,
-                 hold_compilation=False):
+                 hold_compilation=False, heaviside="one"):
+        self._heaviside = validate_heaviside(heaviside)
         self._double = double
         self._compiler_spec = compiler
         self._diff_eqs = _as_tuple(differential_equations)
@@ -274,7 +283,8 @@ class Model:
         # falls back to its default compiler (model.py:77-80, 579-583); the
         # compiler choice is kept here.
         return (_rebuild_model, (self._diff_eqs, self._dep_vars, self._pars,
-                                 self._help_funcs, self._bdcs, self._compiler_spec))
+                                 self._help_funcs, self._bdcs, self._compiler_spec,
+                                 self._heaviside))
 
     def __repr__(self):
         return ("{equations}\n\nVariables\n---------\n"

@@ -19,6 +19,7 @@ There is no CPU implementation behind this module: without ``hipcc`` or the
 built ``libtriflow_hip.so`` it raises.
 """
 
+import contextlib
 import fcntl
 import json
 import logging
@@ -48,11 +49,25 @@ HIPCC_FLAGS = [*os.environ.get("TRIFLOW_HIPCC_OPT", "-O3").split(), "-std=c++17"
                "-ffp-contract=off", "--offload-arch=" + GPU_ARCH,
                *os.environ.get("TRIFLOW_HIPCC_EXTRA", "").split()]
 
+
+@contextlib.contextmanager
+def extra_flags(*flags):
+    """HIPCC_FLAGS with ``flags`` appended for the code objects built inside the block (the flags are
+    part of a code object's cache key): A/B runs of kernel variants inside one process."""
+    saved = list(HIPCC_FLAGS)
+    HIPCC_FLAGS.extend(flags)
+    try:
+        yield
+    finally:
+        HIPCC_FLAGS[:] = saved
+
+
 #: translation units of the host runtime (see the header of csrc/tf_solver.h)
 RUNTIME_SOURCES = ("tf_rt_plan.cpp", "tf_rt_io.cpp", "tf_rt_steps.cpp", "tf_rt_diag.cpp",
                    "tf_solver_sweeps.cpp", "tf_solver_linear.cpp", "tf_rt_probe.cpp", "tf_rt_record.cpp",
                    "tf_rt_stat.cpp", "tf_rt_spectrum.cpp", "tf_rt_extrema.cpp")
 _SKELETON = ("tf_args.h", "tf_math.h", "tf_kernels.h", "tf_crs.h", "tf_coop_hip.h", "tf_cr2_hip.h", "tf_cr3_hip.h",
+             "tf_cr_io.h",
              "tf_node.h", "tf_probe.h", "tf_record.h", "tf_stat.h", "tf_spectrum.h", "tf_extrema.h",
              "tf_entry_hip.h")
 _TU_HEAD = ('#include <hip/hip_runtime.h>\n'

@@ -29,6 +29,24 @@
 // columns: more than a half wavefront) runs with one copy of the columns over the 64 lanes and the two
 // neighbours one after the other.  HIP only.
 #pragma once
+#include "tf_cr_io.h"
+
+// The memory phases (how a chunk comes in, how its records and its share of the next level go out) in
+// their wide form: 16-byte loads and stores, a thread's index mapping worked out once (tf_cr_io.h), the
+// record of a node staged through its dead LDS rows and stored as whole lines.  0: the round-4 loops
+// (A/B runs; the stored values are the same bit for bit).
+#ifndef TF_CR_WIDE_IO
+#define TF_CR_WIDE_IO 1
+#endif
+#ifndef TF_CR_WIDE_LOAD
+#define TF_CR_WIDE_LOAD TF_CR_WIDE_IO
+#endif
+#ifndef TF_CR_WIDE_SHARE
+#define TF_CR_WIDE_SHARE TF_CR_WIDE_IO
+#endif
+#ifndef TF_CR_WIDE_REC
+#define TF_CR_WIDE_REC TF_CR_WIDE_IO
+#endif
 
 template <int BB> struct TfCr3 {
     static constexpr int MAXLEN = TF_CR_MAXLEN, NPOS = MAXLEN + 1;
@@ -42,6 +60,9 @@ template <int BB> struct TfCr3 {
     // b = 8 ... 15: one copy over the 64 lanes, the two neighbours one after the other
     static constexpr bool DUP = NC <= 32;
     static_assert(NC <= 64, "a wavefront holds the augmented columns");
+    typedef TfCrWide<BB> Io;
+    static_assert(Io::RS == RS && Io::PS == PS && Io::oL == oL && Io::oDL == oDL && Io::oU == oU && Io::oYL == oYL &&
+                  Io::oDR == oDR && Io::oYR == oYR, "tf_cr_io.h describes this row layout");
 };
 
 // store to a wave-uniform base + 32-bit lane byte offset (saddr form: no 64-bit lane arithmetic)
@@ -131,17 +152,51 @@ __device__ __forceinline__ void tfk_cr_factor_v4(const TfLevelArgs& a) {
         crel[q] = cok[q] ? (j / BB) * RS + (sd ? oL : oU) + j % BB : 0;
     }
 
+    // (TF_CR_WIDE_REC) the record's blocks 0 - 2 leave through the node's dead rows: Dinv in the DR slots, E
+    // and F where fold_top wants them anyway, then entry lane + 64 q of the record from its slot
+    typedef typename C::Io Io;
+    constexpr int NQ3 = (3 * B2 + 63) / 64;
+    const bool stage = half == 0 && c < NC && !cD;
+    const int soff = cI ? oDR + idc : off1;
+    int srel[NQ3];
+    bool sok[NQ3];
+    if constexpr (TF_CR_WIDE_REC) {
+#pragma unroll
+        for (int q = 0; q < NQ3; ++q) {
+            const int e = lane + 64 * q;
+            sok[q] = e < 3 * B2;
+            srel[q] = sok[q] ? Io::record_slot(e) : 0;
+        }
+    }
+
     TF_STAMP_REAL(a, 30);
     TF_STAMP(a, 0);
     // ---- load: records [node][L, D, U, second part of D][b][b] of a chunk are contiguous;
     //      every request is issued before the first value is used
     {
         const double* src = a.Ablk + (ch.nbase + ch.start) * REC;
+        // (wide form) a thread loads pair q of both halves of the records of its nodes, 16 bytes each, from a
+        // clamped address and without a branch; what lies beyond the chunk is dropped at the LDS write
+        constexpr int NITW = (C::MAXLEN + NT_MIN / B2 - 1) / (NT_MIN / B2);
+        int ndl, wq;
+        bool wact;
+        Io::thread(tid, NT, ndl, wq, wact);
+        const int npi = __builtin_amdgcn_readfirstlane(Io::nodes_per_pass(NT));
+        double2 va[TF_CR_WIDE_LOAD ? NITW : 1], vb[TF_CR_WIDE_LOAD ? NITW : 1];
+        if constexpr (TF_CR_WIDE_LOAD) {
+#pragma unroll
+            for (int it = 0; it < NITW; ++it) {
+                const int nd = ndl + it * npi, ndc = nd < len ? nd : len - 1;
+                const char* p = (const char*)src + (unsigned)((ndc * REC + 2 * wq) * 8);
+                va[it] = *(const double2*)p;
+                vb[it] = *(const double2*)(p + 2 * B2 * 8);
+            }
+        }
         const int n3 = len * 3 * B2;
         constexpr int NIT = (C::MAXLEN * 3 * B2 + NT_MIN - 1) / NT_MIN;
-        double v[NIT], v2[NIT];
+        double v[TF_CR_WIDE_LOAD ? 1 : NIT], v2[TF_CR_WIDE_LOAD ? 1 : NIT];
 #pragma unroll
-        for (int it = 0; it < NIT; ++it) {
+        for (int it = 0; it < (TF_CR_WIDE_LOAD ? 0 : NIT); ++it) {
             const int i = it * NT + tid;
             const int nd = i / (3 * B2), rem = i - nd * 3 * B2, blk = rem / B2, rc = rem - blk * B2;
             v[it] = i < n3 ? src[nd * REC + blk * B2 + rc] : 0.0;
@@ -153,21 +208,49 @@ __device__ __forceinline__ void tfk_cr_factor_v4(const TfLevelArgs& a) {
         if (tid < B2 && ch.has_prev) p0 = prev[tid];
         const double* ys = a.rhs + (ch.nbase + ch.start) * 2 * BB;
         if (with_rhs && tid < len * BB) y0 = ys[(tid / BB) * 2 * BB + tid % BB] + ys[(tid / BB) * 2 * BB + BB + tid % BB];
-        // everything that is not loaded: position 0's L and DL, every DR, yR, yL and the zero slot
-        for (int i = tid; i < (len + 1) * BB * (RS - 3 * BB); i += NT) {
-            const int pr = i / (RS - 3 * BB), o = i - pr * (RS - 3 * BB);
-            sRow[(pr / BB) * PS + (pr % BB) * RS + 3 * BB + o] = 0.0;
-        }
-        if (tid < 3 * B2) {
-            const int blk = tid / B2, rc = tid - blk * B2, r = rc / BB, cc = rc - r * BB;
-            row(0, r)[blk * BB + cc] = 0.0;
-        }
+        if constexpr (TF_CR_WIDE_LOAD) {
+            // position 0 whole; per node the loaded slots (L and U as they are, D = both parts, each "+ 0.0"
+            // of the round-4 loop kept: -0.0 goes in as 0.0) and the slots that are not loaded
+            for (int i = tid; i < PS; i += NT) sRow[i] = 0.0;
+            int ws[2], wz[Io::NZ];
+            bool wd[2];
+            Io::pair(wq, 0, ws[0], wd[0]);
+            Io::pair(wq, 1, ws[1], wd[1]);
 #pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int i = it * NT + tid;
-            const int nd = i / (3 * B2), rem = i - nd * 3 * B2, blk = rem / B2, rc = rem - blk * B2;
-            const int r = rc / BB, cc = rc - r * BB;
-            if (i < n3) row(nd + 1, r)[blk * BB + cc] = v[it] + v2[it];
+            for (int j = 0; j < Io::NZ; ++j) wz[j] = Io::zero_slot(wq, j);
+#pragma unroll
+            for (int it = 0; it < NITW; ++it) {
+                const int nd = ndl + it * npi;
+                double* pos = sRow + (nd + 1) * PS;
+                if (wact && nd < len) {
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const double x = h ? va[it].y : va[it].x, y = h ? vb[it].y : vb[it].x;
+                        pos[ws[h]] = x + (wd[h] ? y : 0.0);
+                        if (!wd[h]) pos[ws[h] + 2 * BB] = y + 0.0;
+                    }
+#pragma unroll
+                    for (int j = 0; j < Io::NZ; ++j)
+                        if (wz[j] >= 0) pos[wz[j]] = 0.0;
+                }
+            }
+        } else {
+            // everything that is not loaded: position 0's L and DL, every DR, yR, yL and the zero slot
+            for (int i = tid; i < (len + 1) * BB * (RS - 3 * BB); i += NT) {
+                const int pr = i / (RS - 3 * BB), o = i - pr * (RS - 3 * BB);
+                sRow[(pr / BB) * PS + (pr % BB) * RS + 3 * BB + o] = 0.0;
+            }
+            if (tid < 3 * B2) {
+                const int blk = tid / B2, rc = tid - blk * B2, r = rc / BB, cc = rc - r * BB;
+                row(0, r)[blk * BB + cc] = 0.0;
+            }
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                const int i = it * NT + tid;
+                const int nd = i / (3 * B2), rem = i - nd * 3 * B2, blk = rem / B2, rc = rem - blk * B2;
+                const int r = rc / BB, cc = rc - r * BB;
+                if (i < n3) row(nd + 1, r)[blk * BB + cc] = v[it] + v2[it];
+            }
         }
         __syncthreads();
         if (tid < B2) row(0, tid / BB)[oU + tid % BB] = p0;
@@ -260,15 +343,28 @@ __device__ __forceinline__ void tfk_cr_factor_v4(const TfLevelArgs& a) {
             //      into its own (dead) row for the last level's back-substitution and z's store
             {
                 double* rec = a.crf + (ch.nbase + ch.node(k)) * 5 * B2;                   // wave-uniform
-                if (grec) {
+                double* rkw = row(k, 0);
+                if constexpr (TF_CR_WIDE_REC) {
+                    // one wavefront owns the row and LDS executes its instructions in order: no barrier
+                    if (stage) {
+#pragma unroll
+                        for (int i = 0; i < BB; ++i) rkw[i * RS + soff] = val[i];
+                    }
+                    TF_WAVE_SYNC();
+                    double sv[NQ3];
+#pragma unroll
+                    for (int q = 0; q < NQ3; ++q) sv[q] = rkw[srel[q]];
+#pragma unroll
+                    for (int q = 0; q < NQ3; ++q)
+                        if (sok[q]) tf_st_u(rec, (unsigned)((lane + 64 * q) * 8), sv[q]);
+                } else if (grec) {
 #pragma unroll
                     for (int i = 0; i < BB; ++i) tf_st_u(rec, goff + (unsigned)(i * BB * 8), val[i]);
                 }
 #pragma unroll
                 for (int q = 0; q < NQ; ++q)
                     if (cok[q]) tf_st_u(rec, (unsigned)((3 * B2 + lane + 64 * q) * 8), cp[q]);
-                double* rkw = row(k, 0);
-                if (keepZ || (keepE && a.fold_top)) {
+                if (!TF_CR_WIDE_REC && (keepZ || (keepE && a.fold_top))) {
 #pragma unroll
                     for (int i = 0; i < BB; ++i) rkw[i * RS + off1] = val[i];
                 }
@@ -307,15 +403,45 @@ __device__ __forceinline__ void tfk_cr_factor_v4(const TfLevelArgs& a) {
     }
     // ---- this chunk's share of the next level's rows: node p gets (L, D, y) of position pe,
     //      node p-1 gets (U, second part of D, second part of y) of position 0
-    for (int i = tid; i < 2 * BB * NO; i += NT) {
-        const int side = i / (BB * NO), rem = i - side * BB * NO, r = rem / NO, o = rem - r * NO;
-        const int nn = side == 0 ? ch.p : ch.pprev;
-        double* rec = a.Anext + ((int64_t)ch.e * a.Lnext.N + nn) * REC;
-        double* rr = a.rhsnext + ((int64_t)ch.e * a.Lnext.N + nn) * 2 * BB;
-        const double* rs = row(side == 0 ? pe : 0, r);
-        if (o < BB) rec[(side == 0 ? 0 : 2) * B2 + r * BB + o] = rs[(side == 0 ? oL : oU) + o];
-        else if (o < 2 * BB) rec[(side == 0 ? 1 : 3) * B2 + r * BB + o - BB] = rs[oDL + o - BB] + rs[oDR + o - BB];
-        else if (with_rhs) rr[(side == 0 ? 0 : BB) + r] = rs[oYL] + rs[oYR];
+    if constexpr (TF_CR_WIDE_SHARE) {
+        // a half record [L | D] or [U | D2] is contiguous: one 16-byte store per thread (tf_cr_io.h)
+        int side, q, rside, rr_r;
+        bool act, ract;
+        Io::share_thread(tid, side, q, act);
+        Io::share_rhs_thread(tid, rside, rr_r, ract);
+        if (act) {
+            const int nn = side == 0 ? ch.p : ch.pprev;
+            double* rec = a.Anext + ((int64_t)ch.e * a.Lnext.N + nn) * REC + side * 2 * B2;
+            const double* rs = row(side == 0 ? pe : 0, 0) + side * 2 * BB;
+            double o[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                int slot;
+                bool dia;
+                Io::pair(q, h, slot, dia);
+                const double* ps = dia ? rs - side * 2 * BB + slot : rs + slot;
+                const double x = ps[0], y = ps[dia ? oDR - oDL : 0];
+                o[h] = dia ? x + y : x;
+            }
+            *(double2*)(rec + 2 * q) = make_double2(o[0], o[1]);
+        }
+        if (ract && with_rhs) {
+            const int nn = rside == 0 ? ch.p : ch.pprev;
+            double* rr = a.rhsnext + ((int64_t)ch.e * a.Lnext.N + nn) * 2 * BB;
+            const double* rs = row(rside == 0 ? pe : 0, rr_r);
+            rr[(rside == 0 ? 0 : BB) + rr_r] = rs[oYL] + rs[oYR];
+        }
+    } else {
+        for (int i = tid; i < 2 * BB * NO; i += NT) {
+            const int side = i / (BB * NO), rem = i - side * BB * NO, r = rem / NO, o = rem - r * NO;
+            const int nn = side == 0 ? ch.p : ch.pprev;
+            double* rec = a.Anext + ((int64_t)ch.e * a.Lnext.N + nn) * REC;
+            double* rr = a.rhsnext + ((int64_t)ch.e * a.Lnext.N + nn) * 2 * BB;
+            const double* rs = row(side == 0 ? pe : 0, r);
+            if (o < BB) rec[(side == 0 ? 0 : 2) * B2 + r * BB + o] = rs[(side == 0 ? oL : oU) + o];
+            else if (o < 2 * BB) rec[(side == 0 ? 1 : 3) * B2 + r * BB + o - BB] = rs[oDL + o - BB] + rs[oDR + o - BB];
+            else if (with_rhs) rr[(side == 0 ? 0 : BB) + r] = rs[oYL] + rs[oYR];
+        }
     }
     TF_STAMP(a, 20);
     if (a.fold_top) {

@@ -349,6 +349,73 @@ def block_mask(nvar, pat_eq, pat_var):
     return m
 
 
+#: widest block ``mp * nvar`` whose level-1 walks hold their working set in registers: the bound of the
+#: twisted walks (``tf_twist_h`` in csrc/tf_kernels.h carries the same 6) and of the factored outermost U block
+REGISTER_BLOCK_MAX = 6
+
+
+def outer_u_form(nvar, mp, pat_eq, pat_var, pat_off, j_uniform, j_alias, blk_nz):
+    """The factored form of the outermost block of the stored pivot rows U~.
+
+    The elimination never touches a row's outermost block, so ``U~[mp-1] = Dinv A(j, j +- mp)`` with
+    ``A(j, j +- mp) = -c J(j, j +- mp)`` as the value table gives it: the level-1 walks can store
+    the columns ``Dinv[:, S]`` instead, S = the equations that reach offset ``+-mp`` at all, and the
+    back-substitution rebuilds the block from them and the Jacobian planes.  Per direction (index 0:
+    offset ``+mp``, the down walk; index 1: ``-mp``, the up walk) this gives the pattern of the outer
+    block, S, and the value planes to load (a proportional entry counts as the plane it aliases, a
+    node-independent one is evaluated).  Returns None unless, for both directions,
+
+        (entries of Dinv[:, S] inside the block mask) + (planes loaded)
+            < (entries of the outer U~ block inside the block mask)
+
+    -- or if ``TRIFLOW_U_OUTER=0`` asks for the stored form (A/B runs).  Scalar models exchange rows
+    (the invariant does not hold) and never qualify: 1 + 0 < 1 is false.  Blocks too wide for the
+    registers (``mp * nvar > REGISTER_BLOCK_MAX``, the bound of the twisted walks, tf_twist_h) keep the stored form as
+    well: their walks spill already, and the columns of Dinv held for the store and the rebuilt block
+    cost registers (wide4, 13 < 16 by the count: tfk_l1_factor_rhs 112 -> 132 bytes of scratch,
+    tfk_l1_backsub_u occupancy 4 -> 3)."""
+    if os.environ.get("TRIFLOW_U_OUTER", "1") == "0" or nvar < 2 or mp * nvar > REGISTER_BLOCK_MAX:
+        return None
+    nnz = len(pat_eq)
+    form = dict(nz=[], rows=[], planes=[])
+    for off in (mp, -mp):
+        ks = [k for k in range(nnz) if pat_off[k] == off]
+        nz = [[False] * nvar for _ in range(nvar)]
+        for k in ks:
+            nz[pat_eq[k]][pat_var[k]] = True
+        rows = [any(nz[e]) for e in range(nvar)]
+        planes = sorted({(j_alias[k] if j_alias[k] >= 0 else k) for k in ks if not j_uniform[k]})
+        stored = sum(1 for r in range(nvar) for k in range(nvar) if rows[k] and blk_nz[r][k])
+        block = sum(1 for r in range(nvar) for c in range(nvar) if blk_nz[r][c])
+        if not stored + len(planes) < block:
+            return None
+        form["nz"].append(nz)
+        form["rows"].append(rows)
+        form["planes"].append(planes)
+    return form
+
+
+def _outer_u_lines(form, nvar, nnz):
+    """The header lines of outer_u_form (none for a model that keeps the stored form)."""
+    if form is None:
+        return []
+
+    def bools(values):
+        return "{%s}" % ", ".join("true" if v else "false" for v in values)
+    return [
+        "// outermost block of the stored pivot rows in factored form (outer_u_form); [0]: offset +mp, [1]: -mp",
+        "#define TF_UOUT_FACT 1",
+        "// pattern of the outer block of A: [direction][equation][variable]",
+        "static constexpr bool tf_uout_nz[2][%d][%d] = {%s};" % (
+            nvar, nvar, ", ".join("{%s}" % ", ".join(bools(row) for row in nz) for nz in form["nz"])),
+        "// S, the equations that reach the outer offset: the columns of Dinv that are stored",
+        "static constexpr bool tf_uout_row[2][%d] = {%s};" % (nvar, ", ".join(bools(r) for r in form["rows"])),
+        "// the value planes that feed the outer block",
+        "static constexpr bool tf_uout_ld[2][%d] = {%s};" % (
+            max(nnz, 1), ", ".join(bools([k in planes for k in range(max(nnz, 1))]) for planes in form["planes"])),
+    ]
+
+
 def lower_model(model, parvec_mask=0, seg=8, sweep_block=64):
     """Returns ``(source, spec)``: the per-model translation unit (without the
     skeleton includes' contents) and the dict of constants the runtime needs."""
@@ -423,6 +490,7 @@ def lower_model(model, parvec_mask=0, seg=8, sweep_block=64):
 
     blk_nz = block_mask(nvar, pat_eq, pat_var)
     blk_full = all(all(row) for row in blk_nz)
+    u_outer = outer_u_form(nvar, mp, pat_eq, pat_var, pat_off, j_uniform, j_alias, blk_nz)
     hc_list = [src_ for src_, _ in sorted(host_consts.items(), key=lambda kv: kv[1])]
     par_is_vec = [1 if (parvec_mask >> k) & 1 else 0 for k in range(len(pars))] + [0] * len(hc_list)
     if len(pars) + len(hc_list) > 16:
@@ -448,6 +516,7 @@ def lower_model(model, parvec_mask=0, seg=8, sweep_block=64):
         arr("tf_par_is_vec", par_is_vec, "bool"),
         arr("tf_j_uniform", j_uniform, "bool"),
         arr("tf_j_alias", j_alias), arr("tf_j_alias_scale", [_dbl(v) for v in j_alias_scale], "double"),
+        *_outer_u_lines(u_outer, nvar, nnz),
         "TF_DEVICE void tf_eval_F(const double (&w)[TF_NVAR + TF_NH][2 * TF_MP + 1], "
         "const double* par, double dx, double xc, double* F) {",
         body("F", f_c, emit_f),
@@ -467,7 +536,7 @@ def lower_model(model, parvec_mask=0, seg=8, sweep_block=64):
                 sweep_block=sweep_block, uses_x=int(uses_x), parvec_mask=int(parvec_mask),
                 b2=mp * nvar, pat_eq=pat_eq, pat_var=pat_var, pat_off=pat_off, j_uniform=j_uniform,
                 j_alias=j_alias, j_alias_scale=j_alias_scale,
-                blk_nz=blk_nz, fields=fields, pars=pars, heaviside=mode)
+                blk_nz=blk_nz, u_outer=u_outer, fields=fields, pars=pars, heaviside=mode)
     return src, spec
 
 

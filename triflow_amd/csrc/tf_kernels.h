@@ -35,6 +35,9 @@
 #define TF_W (2 * TF_MP + 1)
 #define TF_NF (TF_NVAR + TF_NH)
 #define TF_B2 (TF_MP * TF_NVAR)          // block size of the reduced (interface) systems
+#ifndef TF_UOUT_FACT
+#define TF_UOUT_FACT 0                   // (generated for the models that take the factored form: TfUOut)
+#endif
 
 #include "tf_math.h"
 
@@ -681,9 +684,11 @@ TF_DEVICE void tf_mm_sub(double (&C)[B][B], const double (&A)[B][B], const doubl
             C[r][c] = acc;
         }
 }
-// C = A * Bm
-template <int B>
-TF_DEVICE void tf_mm(double (&C)[B][B], const double (&A)[B][B], const double (&Bm)[B][B]) {
+// C = A * Bm.  `term(k)`: whether row k of Bm can be non-zero at all; the terms of the others are left
+// out, those that stay keep their order (TfULoad::outer: the rows of an outermost block of A).
+struct TfEveryTerm { TF_DEVICE_M constexpr bool operator()(int) const { return true; } };
+template <int B, class Term = TfEveryTerm>
+TF_DEVICE void tf_mm(double (&C)[B][B], const double (&A)[B][B], const double (&Bm)[B][B], Term term = Term()) {
     typedef TfMask<B> M;
 #pragma unroll
     for (int r = 0; r < B; ++r)
@@ -692,7 +697,7 @@ TF_DEVICE void tf_mm(double (&C)[B][B], const double (&A)[B][B], const double (&
             double acc = 0.0;
 #pragma unroll
             for (int k = 0; k < B; ++k)
-                if (M::nz(r, c) && M::nz(r, k) && M::nz(k, c)) acc = tf_fma(A[r][k], Bm[k][c], acc);
+                if (M::nz(r, c) && M::nz(r, k) && M::nz(k, c) && term(k)) acc = tf_fma(A[r][k], Bm[k][c], acc);
             C[r][c] = acc;
         }
 }
@@ -880,6 +885,38 @@ struct TfRowsL1 {
         request(i, raw);
         decode(i, raw, row);
     }
+#if TF_UOUT_FACT
+    // The outermost block of a row alone, A(i, i + TF_MP) (up: A(i, i - TF_MP)), for the readers of
+    // the factored U~ (TfULoad): only the planes that feed it are requested (tf_uout_ld), and
+    // decode_outer gives the bits of decode() -- the same -c * jv, the same scaling of a
+    // proportional entry, and the clamped ends, where the fold empties an outermost block (its
+    // target is a block nearer the diagonal: nothing is ever added to an outermost one).
+    TF_DEVICE_M void request_outer(int i, bool up, Raw& r) const {
+        const unsigned off = tf_off8(a.L, pg, i);
+#pragma unroll
+        for (int k = 0; k < TF_NNZ; ++k) {
+            if (TF_JU(k)) r.jv[k] = ju.v[k];
+            else if (tf_uout_ld[0][k] && tf_uout_ld[1][k]) r.jv[k] = tf_ldp(a.Jv, k, a.L.plane, off);
+            else if (tf_uout_ld[0][k] || tf_uout_ld[1][k]) {
+                if (up == tf_uout_ld[1][k]) r.jv[k] = tf_ldp(a.Jv, k, a.L.plane, off);
+            }
+        }
+    }
+    TF_DEVICE_M void decode_outer(int i, bool up, const Raw& raw, double (&blk)[TF_NVAR][TF_NVAR]) const {
+        tf_blk_zero<TF_NVAR>(blk);
+#pragma unroll
+        for (int k = 0; k < TF_NNZ; ++k) {
+            if (tf_pat_off[k] != TF_MP && tf_pat_off[k] != -TF_MP) continue;
+            if (up != (tf_pat_off[k] < 0)) continue;
+            const double jv = TF_JA(k) ? tf_j_alias_scale[k] * raw.jv[tf_j_alias[k] >= 0 ? tf_j_alias[k] : 0] : raw.jv[k];
+            blk[tf_pat_eq[k]][tf_pat_var[k]] = -a.c * jv;
+        }
+        if (!a.L.periodic) {
+            const int gl = start + i, gr = a.L.N - 1 - gl;
+            if (up ? gl < TF_MP : gr < TF_MP) tf_blk_zero<TF_NVAR>(blk);
+        }
+    }
+#endif
 };
 
 // level >= 2: explicit block-tridiagonal rows [3][b][b]
@@ -927,6 +964,77 @@ struct TfRowsBT {
 template <class Rows>
 TF_DEVICE_M constexpr bool tf_kept(int r, int k) { return !Rows::MASKED || TfMask<Rows::B>::nz(r, k); }
 
+// ---- the outermost block of the stored pivot rows, in factored form -------------
+// The elimination of tfk_chunk_body never touches a row's outermost block: the update
+// R[q][c] -= R[q][0] Un[c-1] runs over c = 1..MP, and for the rows q >= 1 the outermost column is
+// q + MP > MP.  No rows are exchanged for B > 1, so when a row becomes the pivot row R[0][MP] is
+// still what Rows::decode made of the value table, and the stored block is
+//     Un[MP-1] = tf_mm(Dinv, A(j, j +- MP)),
+// which depends on Dinv only through the columns of S, the equations that reach offset +- MP at all
+// (every other row of the outer block of A is structurally zero).  Where that is fewer values
+// (TF_UOUT_FACT, codegen.outer_u_form: Dinv[:, S] plus the value planes that feed the block, against
+// the block), the walks store Dinv[:, S] in the plane slots of that block -- entry (r, k) in the slot
+// of (r, k), the other slots are never touched -- and every reader of Ut rebuilds the block with
+// the same product restricted to k in S: the terms left out multiply exact zeros, so the bits are
+// those of the stored block up to the sign of a zero.
+template <class Rows> struct TfUOut {
+    static constexpr bool ON = false;
+    TF_DEVICE_M static constexpr bool row(bool, int) { return true; }
+    static constexpr int RING = Rows::B * Rows::B;            // doubles of the outermost block in a ring node
+};
+#if TF_UOUT_FACT
+// doubles a node in flight holds for its outermost block: Dinv[:, S] and the value planes
+constexpr int tf_uout_count(int dir) {
+    int n = 0;
+    for (int k = 0; k < TF_NVAR; ++k) n += tf_uout_row[dir][k] ? TF_NVAR : 0;
+    for (int k = 0; k < TF_NNZ; ++k) n += tf_uout_ld[dir][k] ? 1 : 0;
+    return n;
+}
+template <> struct TfUOut<TfRowsL1> {
+    static constexpr bool ON = true;
+    static_assert(!TfRowsL1::PIVOT, "exchanged rows do not keep their outermost block");
+    TF_DEVICE_M static constexpr bool row(bool up, int k) { return up ? tf_uout_row[1][k] : tf_uout_row[0][k]; }
+    static constexpr int RING = tf_uout_count(0) > tf_uout_count(1) ? tf_uout_count(0) : tf_uout_count(1);
+};
+#endif
+
+// The one reader of the factored pivot rows of a node (tfk_backsub_body, tfk_backsub_twist_body).
+// request(): the stored entries and the value planes of the outer block, all put on their way
+// together; outer(): the outermost block, rebuilt where it is used, so that a ring of nodes in
+// flight holds the smaller form.  `up`: the node's row was stored by the up walk.
+// (the stored form has nothing to rebuild: its readers load the blocks as they lie in Ut)
+template <class Rows, int UW, bool FACT = TfUOut<Rows>::ON> struct TfULoad {
+    static constexpr bool FACTORED = false;
+    struct Outer {};
+    TF_DEVICE_M TfULoad(const TfLevelArgs&, int) {}
+};
+template <class Rows, int UW> struct TfULoad<Rows, UW, true> {
+    static constexpr int B = Rows::B;
+    static constexpr bool FACTORED = true;
+    typedef typename Rows::Raw Outer;
+    Rows rows;
+    TF_DEVICE_M TfULoad(const TfLevelArgs& a, int pg) : rows(a, pg) {}
+    // U[UW-1] receives Dinv[:, S]
+    TF_DEVICE_M void request(const TfLevelArgs& a, unsigned off, int i, bool up, double (&U)[UW][B][B], Outer& o) const {
+#pragma unroll
+        for (int c = 0; c < UW; ++c)
+#pragma unroll
+            for (int r = 0; r < B; ++r)
+#pragma unroll
+                for (int k = 0; k < B; ++k) {
+                    U[c][r][k] = 0.0;
+                    if (tf_kept<Rows>(r, k) && (c < UW - 1 || TfUOut<Rows>::row(up, k)))
+                        U[c][r][k] = tf_ldp(a.Ut, (c * B + r) * B + k, a.L.plane, off);
+                }
+        rows.request_outer(i, up, o);
+    }
+    TF_DEVICE_M void outer(int i, bool up, const double (&U)[UW][B][B], const Outer& o, double (&Uo)[B][B]) const {
+        double A[B][B];
+        rows.decode_outer(i, up, o, A);
+        tf_mm<B>(Uo, U[UW - 1], A, [up](int k) { return TfUOut<Rows>::row(up, k); });
+    }
+};
+
 // Rows requested ahead of their use in the level-1 walks: one (0) or two (1).  Two rows hide more
 // latency but cost 2 x (nnz + nvar) registers in kernels that already overflow into AGPRs; with the
 // walks bound by their instruction stream the moves cost more than the latency:
@@ -959,6 +1067,7 @@ constexpr int tf_ring_depth(int nd, int other = 40) {
 // h = mI: the up half is empty and everything reduces to the one-sided form.  So do solvers whose
 // chunks fill the GPU anyway (a.twist = 0: more than TF_TWIST_MAX_CHUNKS; there the second walk
 // only adds the middle system: 8 members per GPU -3 %, config 5 -1.5 %).
+// (codegen.REGISTER_BLOCK_MAX is this 6: blocks up to that width also take the factored outermost U block)
 template <int B, int MP>
 TF_DEVICE int tf_twist_h(int mI, int enabled) {
     return (enabled && MP * B <= 6 && mI >= 4 * MP) ? (mI + 1) / 2 : mI;
@@ -1157,6 +1266,14 @@ TF_DEVICE void tf_tips_out(const TfLevelArgs& a, const Rows& rows, int pg,
     }
 }
 
+// The pivot rows a factorisation walk keeps in Ut: the down walk all of them, or, with a.respike, each
+// walk those of its half (hdn = tf_twist_h: the nodes of the down half).  The one place that says so:
+// the walk stores a row's blocks and, for the factored outermost block, its columns of Dinv at two
+// points of a pivot, and a reader cannot tell a row that has one form from a row that has the other.
+// (a macro, not a function: the walks' code is to the instruction what it was with the expression
+// written out)
+#define TF_KEEP_U(a, DIR, j, hdn, mI) ((a).respike ? ((DIR) > 0 ? (j) < (hdn) : (j) < (mI) - (hdn)) : (DIR) > 0)
+
 // ---- interior elimination of one chunk in one direction --------------------
 // DIR = +1 walks down (local j <-> node j), DIR = -1 walks up (local j <-> node
 // mI-1-j, offsets mirrored).  SPIKE: also carry the coupling to the separator
@@ -1343,6 +1460,19 @@ TF_DEVICE void tfk_chunk_body(const TfLevelArgs& a, int pg, double* ylds = nullp
                     for (int k = 0; k < B; ++k)
                         if (tf_kept<Rows>(r, k)) slot[(r * B + k) * 64] = Dinv[r][k];
             }
+            if constexpr (TfUOut<Rows>::ON && STORE_U) {
+                // the outermost block of the pivot row leaves in factored form (TfUOut): the columns of
+                // Dinv it depends on, in the plane slots of that block
+                if (TF_KEEP_U(a, DIR, j, hdn, mI)) {
+                    const unsigned off = tf_off8(L, pg, node(j));
+#pragma unroll
+                    for (int r = 0; r < B; ++r)
+#pragma unroll
+                        for (int k = 0; k < B; ++k)
+                            if (tf_kept<Rows>(r, k) && TfUOut<Rows>::row(DIR < 0, k))
+                                tf_stp(a.Ut, ((UW - 1) * B + r) * B + k, L.plane, off, Dinv[r][k]);
+                }
+            }
         }
         if (!PIV) fetch(MP, j + MP);
         if (ROLE == 1) {
@@ -1370,7 +1500,7 @@ TF_DEVICE void tfk_chunk_body(const TfLevelArgs& a, int pg, double* ylds = nullp
         // (a.respike: E and y of the first elimination are not kept, and each walk keeps the U of
         // its half, see tfk_l1_fwd2)
         const bool keep = KNOWN || !a.respike;
-        const bool keep_u = a.respike ? (DIR > 0 ? j < hdn : j < mI - hdn) : DIR > 0;
+        const bool keep_u = TF_KEEP_U(a, DIR, j, hdn, mI);
         if (STORE_U || STORE_Y) {
             const unsigned off = tf_off8(L, pg, node(j));
             if (STORE_U && keep_u) {
@@ -1381,7 +1511,8 @@ TF_DEVICE void tfk_chunk_body(const TfLevelArgs& a, int pg, double* ylds = nullp
 #pragma unroll
                         for (int k = 0; k < B; ++k) {
                             if (!tf_kept<Rows>(r, k)) continue;
-                            tf_stp(a.Ut, (c * B + r) * B + k, L.plane, off, Un[c][r][k]);
+                            if (!TfUOut<Rows>::ON || c < UW - 1)     // (the outermost block: stored above)
+                                tf_stp(a.Ut, (c * B + r) * B + k, L.plane, off, Un[c][r][k]);
                             if (ES && keep && c < MP)
                                 tf_stp(a.Et, (c * B + r) * B + k, L.plane, off, En[ES && c < MP ? c : 0][r][k]);
                         }
@@ -1536,7 +1667,7 @@ TF_DEVICE void tfk_rhs_follow_body(const TfLevelArgs& a, int pg, double* xch, do
             for (int t = 0; t < MP; ++t) tf_mm_sub<B>(Es[q][t], M, En[t]);
         }
         // (a.respike: E and y of the first elimination are not kept)
-        const bool keep_u = a.respike ? (DIR > 0 ? j < hdn : j < mI - hdn) : DIR > 0;
+        const bool keep_u = TF_KEEP_U(a, DIR, j, hdn, mI);
         if ((STORE_U || STORE_Y) && !a.respike) {
             const unsigned off = tf_off8(L, pg, node(j));
             if (STORE_U && keep_u) {
@@ -1870,26 +2001,44 @@ TF_DEVICE void tfk_backsub_body(const TfLevelArgs& a, int pg) {
     }
     // the factors of node j-1 are requested before node j is processed, so one
     // HBM latency is paid per chunk, not per node
-    struct Node { double y[B]; double U[UW][B][B]; double E[WITH_E ? MP : 1][B][B]; };
+    typedef TfULoad<Rows, UW> ULoad;
+    const ULoad uload(a, pg);
+    // (the loader's part of a node is a base: empty for the stored form)
+    struct Node : ULoad::Outer { double y[B]; double U[UW][B][B]; double E[WITH_E ? MP : 1][B][B]; };
     auto load = [&](int j, Node& n) {
         const unsigned off = tf_off8(L, pg, j);
 #pragma unroll
         for (int r = 0; r < B; ++r) n.y[r] = tf_ldp(a.yt, r, L.plane, off);
+        if constexpr (ULoad::FACTORED) {
+            uload.request(a, off, j, false, n.U, n);
 #pragma unroll
-        for (int c = 0; c < UW; ++c)
+            for (int c = 0; c < (WITH_E ? MP : 0); ++c)
 #pragma unroll
-            for (int r = 0; r < B; ++r)
+                for (int r = 0; r < B; ++r)
 #pragma unroll
-                for (int k = 0; k < B; ++k) {
-                    const bool kept = tf_kept<Rows>(r, k);
-                    n.U[c][r][k] = kept ? tf_ldp(a.Ut, (c * B + r) * B + k, L.plane, off) : 0.0;
-                    if (WITH_E && c < MP) n.E[WITH_E && c < MP ? c : 0][r][k] = kept ? tf_ldp(a.Et, (c * B + r) * B + k, L.plane, off) : 0.0;
-                }
+                    for (int k = 0; k < B; ++k)
+                        n.E[c][r][k] = tf_kept<Rows>(r, k) ? tf_ldp(a.Et, (c * B + r) * B + k, L.plane, off) : 0.0;
+        } else {
+            // (the stored form keeps the loop it always had instead of going through TfULoad: routed
+            // through the loader the same loads came out in another order, and the code objects of
+            // the models that keep this form would no longer be the ones they were -- a change of
+            // the layout of Ut has to be made here and in TfULoad::request)
+#pragma unroll
+            for (int c = 0; c < UW; ++c)
+#pragma unroll
+                for (int r = 0; r < B; ++r)
+#pragma unroll
+                    for (int k = 0; k < B; ++k) {
+                        const bool kept = tf_kept<Rows>(r, k);
+                        n.U[c][r][k] = kept ? tf_ldp(a.Ut, (c * B + r) * B + k, L.plane, off) : 0.0;
+                        if (WITH_E && c < MP) n.E[WITH_E && c < MP ? c : 0][r][k] = kept ? tf_ldp(a.Et, (c * B + r) * B + k, L.plane, off) : 0.0;
+                    }
+        }
     };
     // TF_BACKSUB_DEPTH nodes of factors in flight per thread: the walk is a chain of loads
     // (few wavefronts: one lane per chunk), so its speed is the number of requests that are
     // outstanding, not the arithmetic.  The ring is unrolled: every index is static.
-    constexpr int D = tf_ring_depth(B + UW * B * B + (WITH_E ? MP * B * B : 0));
+    constexpr int D = tf_ring_depth(B + (UW - 1) * B * B + TfUOut<Rows>::RING + (WITH_E ? MP * B * B : 0));
     Node ring[D];
 #pragma unroll
     for (int d = 0; d < D; ++d)
@@ -1905,7 +2054,12 @@ TF_DEVICE void tfk_backsub_body(const TfLevelArgs& a, int pg) {
 #pragma unroll
             for (int r = 0; r < B; ++r) x[r] = cur.y[r];
 #pragma unroll
-            for (int c = 0; c < UW; ++c) tf_mv_sub<B>(x, cur.U[c], xn[c]);
+            for (int c = 0; c < (ULoad::FACTORED ? UW - 1 : UW); ++c) tf_mv_sub<B>(x, cur.U[c], xn[c]);
+            if constexpr (ULoad::FACTORED) {
+                double Uo[B][B];
+                uload.outer(j, false, cur.U, cur, Uo);
+                tf_mv_sub<B>(x, Uo, xn[UW - 1]);
+            }
             if (WITH_E) {
 #pragma unroll
                 for (int c = 0; c < MP; ++c) tf_mv_sub<B>(x, cur.E[WITH_E ? c : 0], sa[c]);
@@ -1980,7 +2134,10 @@ TF_DEVICE void tfk_backsub_twist_body(const TfLevelArgs& a, int pg, int dir,
     // the last pivot lies the separator; twisted, the MP nodes next to the middle are solved there
     const int jstart = hu == 0 ? mI - 1 : (dir == 0 ? h - MP - 1 : hu - MP - 1);
     auto nat = [&](int j) { return dir == 0 ? j : mI - 1 - j; };
-    auto ldU = [&](int node_nat, double (&U)[MP][B][B], double (&y)[B]) {
+    // (a node's row was stored by the walk that owns its half: TfULoad's `up`)
+    typedef TfULoad<Rows, MP> ULoad;
+    const ULoad uload(a, pg);
+    auto ldU = [&](int node_nat, double (&U)[MP][B][B], double (&y)[B], typename ULoad::Outer& o) {
         const unsigned off = tf_off8(L, pg, node_nat);
         if (YLDS) {
             // the down walk numbers its nodes from the top of the chunk, the up walk from the bottom
@@ -1991,13 +2148,28 @@ TF_DEVICE void tfk_backsub_twist_body(const TfLevelArgs& a, int pg, int dir,
 #pragma unroll
             for (int r = 0; r < B; ++r) y[r] = tf_ldp(a.yt, r, L.plane, off);
         }
+        if constexpr (ULoad::FACTORED) {
+            uload.request(a, off, node_nat, node_nat >= h, U, o);
+        } else {
+            // (the stored form's own loop, as in tfk_backsub_body: see there)
 #pragma unroll
-        for (int c = 0; c < MP; ++c)
+            for (int c = 0; c < MP; ++c)
 #pragma unroll
-            for (int r = 0; r < B; ++r)
+                for (int r = 0; r < B; ++r)
 #pragma unroll
-                for (int k = 0; k < B; ++k)
-                    U[c][r][k] = tf_kept<Rows>(r, k) ? tf_ldp(a.Ut, (c * B + r) * B + k, L.plane, off) : 0.0;
+                    for (int k = 0; k < B; ++k)
+                        U[c][r][k] = tf_kept<Rows>(r, k) ? tf_ldp(a.Ut, (c * B + r) * B + k, L.plane, off) : 0.0;
+        }
+    };
+    // the same with the outermost block in place: the rows of the middle system
+    auto ldU_whole = [&](int node_nat, double (&U)[MP][B][B], double (&y)[B]) {
+        typename ULoad::Outer o;
+        ldU(node_nat, U, y, o);
+        if constexpr (ULoad::FACTORED) {
+            double Uo[B][B];
+            uload.outer(node_nat, node_nat >= h, U, o, Uo);
+            tf_blk_copy<B>(U[MP - 1], Uo);
+        }
     };
     // a.upd_n (the launch that holds the re-elimination, YLDS): the solve is the last one of a time
     // step and what leaves is the new state, base + c0 x (one term) or base + (c0 k0 + c1 x) -- the
@@ -2050,9 +2222,10 @@ TF_DEVICE void tfk_backsub_twist_body(const TfLevelArgs& a, int pg, int dir,
         }
     }
     // the factors of the first streamed nodes are requested before the middle system is solved
-    struct Node { double y[B]; double U[MP][B][B]; Upd u; };
-    auto load = [&](int j, Node& n) { ldU(nat(j), n.U, n.y); upd_load(nat(j), n.u); };
-    constexpr int D = tf_ring_depth(3 * B + MP * B * B, 2 * (MP * B) * (MP * B) + 2 * MP * B + MP * B * B + B);
+    struct Node : ULoad::Outer { double y[B]; double U[MP][B][B]; Upd u; };
+    auto load = [&](int j, Node& n) { ldU(nat(j), n.U, n.y, n); upd_load(nat(j), n.u); };
+    constexpr int D = tf_ring_depth(3 * B + (MP - 1) * B * B + TfUOut<Rows>::RING,
+                                    2 * (MP * B) * (MP * B) + 2 * MP * B + MP * B * B + B);
     Node ring[D];
 #pragma unroll
     for (int d = 0; d < D; ++d)
@@ -2064,7 +2237,7 @@ TF_DEVICE void tfk_backsub_twist_body(const TfLevelArgs& a, int pg, int dir,
         // rows of the down half, last first, substituted into each other (T1 is unit upper triangular)
 #pragma unroll
         for (int k = MP - 1; k >= 0; --k) {
-            ldU(h - MP + k, Uk, yk);
+            ldU_whole(h - MP + k, Uk, yk);
 #pragma unroll
             for (int i = 0; i < B; ++i) {
                 Tg[k * B + i] = yk[i];
@@ -2097,7 +2270,7 @@ TF_DEVICE void tfk_backsub_twist_body(const TfLevelArgs& a, int pg, int dir,
         // a = Tg - Tc b.  Rows of the up half: x_r + sum_c U'_r[c] x_{r-1-c} = y'_r
 #pragma unroll
         for (int k = 0; k < MP; ++k) {
-            ldU(h + k, Uk, yk);
+            ldU_whole(h + k, Uk, yk);
 #pragma unroll
             for (int i = 0; i < B; ++i) {
                 g2[k * B + i] = yk[i];
@@ -2164,7 +2337,12 @@ TF_DEVICE void tfk_backsub_twist_body(const TfLevelArgs& a, int pg, int dir,
 #pragma unroll
             for (int r = 0; r < B; ++r) x[r] = cur.y[r];
 #pragma unroll
-            for (int c = 0; c < MP; ++c) tf_mv_sub<B>(x, cur.U[c], xn[c]);
+            for (int c = 0; c < (ULoad::FACTORED ? MP - 1 : MP); ++c) tf_mv_sub<B>(x, cur.U[c], xn[c]);
+            if constexpr (ULoad::FACTORED) {
+                double Uo[B][B];
+                uload.outer(nat(j), dir != 0, cur.U, cur, Uo);
+                tf_mv_sub<B>(x, Uo, xn[MP - 1]);
+            }
 #pragma unroll
             for (int c = MP - 1; c > 0; --c)
 #pragma unroll

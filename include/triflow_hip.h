@@ -382,6 +382,34 @@ int tf_extrema_fetch(tf_extrema*, int32_t which, double* out, int64_t max_rows, 
 /* rows of observer `which` recorded and not fetched yet (no wait) */
 int tf_extrema_pending(tf_extrema*, int32_t which, int64_t* rows);
 
+/* ---- device histograms: value distributions of model expressions on a resident state slot ----
+ * code_object: the model's code object rebuilt with the generated histogram block
+ * (codegen.lower_histograms; built with the solver's parameter layout and sweep segment).  Only such a code
+ * object holds tfk_hist_partial and tfk_hist_final: they are not in the kernel table (tf_kernel_name), are
+ * resolved by name here and are not covered by tf_timing_get.  geometry[nhist][6]: the expression of the
+ * block (histograms may share one; the expressions are numbered in the order the histograms first use
+ * them), the number of bins (1 ... 256), the rows of the histogram's ring in device memory and the window
+ * of nodes (start, stop, step: slice.indices(N), step >= 1).  The nbins + 1 edges (finite, strictly
+ * increasing) are data of the handle: set_edges before the first record.  A record is queued on the
+ * solver's stream (no host wait unless the ring is full: then all of it comes over in one copy first) and
+ * writes one row [nsys][nbins + 3] of counts as doubles: bin i counts edges[i] <= v < edges[i + 1] over the
+ * window nodes, the last bin also v == edges[nbins]; then v < edges[0], v > edges[nbins] and the NaNs.  A
+ * histogram set belongs to its solver: destroy it first. */
+typedef struct tf_histogram tf_histogram;
+int tf_histogram_create(tf_solver*, const void* code_object, size_t code_size, int32_t nhist,
+                        const int32_t* geometry, int32_t nconst, tf_histogram** out);
+void tf_histogram_destroy(tf_histogram* histogram);
+int tf_histogram_set_consts(tf_histogram*, const double* values /*[nsys][nconst]*/, int32_t nconst);
+/* coordinates of the nodes (expressions that read x); ignored when the solver's model reads x itself */
+int tf_histogram_set_x(tf_histogram*, const double* x /*[nsys][N]*/);
+int tf_histogram_set_edges(tf_histogram*, int32_t which, const double* edges, int32_t nedges);
+int tf_histogram_record(tf_histogram*, int32_t which, int32_t slot);
+/* waits, then hands over up to max_rows rows of histogram `which` not fetched before, oldest first,
+ * out[rows][nsys][nbins + 3] */
+int tf_histogram_fetch(tf_histogram*, int32_t which, double* out, int64_t max_rows, int64_t* rows);
+/* rows of histogram `which` recorded and not fetched yet (no wait) */
+int tf_histogram_pending(tf_histogram*, int32_t which, int64_t* rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,15 @@ SIGNATURES = {
     "tf_extrema_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "tf_extrema_fetch": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int64, c_int64_p]),
     "tf_extrema_pending": (C.c_int, [C.c_void_p, C.c_int32, c_int64_p]),
+    "tf_histogram_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, c_int32_p, C.c_int32,
+                                      C.POINTER(C.c_void_p)]),
+    "tf_histogram_destroy": (None, [C.c_void_p]),
+    "tf_histogram_set_consts": (C.c_int, [C.c_void_p, c_double_p, C.c_int32]),
+    "tf_histogram_set_x": (C.c_int, [C.c_void_p, c_double_p]),
+    "tf_histogram_set_edges": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int32]),
+    "tf_histogram_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "tf_histogram_fetch": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int64, c_int64_p]),
+    "tf_histogram_pending": (C.c_int, [C.c_void_p, C.c_int32, c_int64_p]),
 }
 
 
@@ -539,7 +548,7 @@ class DeviceSolver:
 
 
 class _DeviceObserver:
-    """What ``tf_probe``, ``tf_record``, ``tf_stat``, ``tf_spectrum`` and ``tf_extrema`` share: a code object of expressions bound to one solver, the
+    """What ``tf_probe``, ``tf_record``, ``tf_stat``, ``tf_spectrum``, ``tf_extrema`` and ``tf_histogram`` share: a code object of expressions bound to one solver, the
     x plane and the host constants of the expressions.  ``_prefix``: of the C entry points, ``_noun``:
     what the error message calls the set."""
 
@@ -732,3 +741,35 @@ class DeviceExtrema(_DeviceObserver):
         raw = self._fetch(1 + 4 * self.max_count[which], int(which))
         self.fetched += raw.size
         return raw
+
+
+class DeviceHistogram(_DeviceObserver):
+    """``tf_histogram``: the histogram kernels of one histogram set bound to one solver, the edges and the
+    rings."""
+
+    _prefix, _noun = "tf_histogram", "histogram"
+
+    def __init__(self, solver, code, geometry, edges, nconst):
+        """``geometry``: per histogram ``(expression, number of bins, rows of the ring, start, stop, step)``;
+        ``edges``: per histogram, its ``nbins + 1`` edges (uploaded here: they are data of the handle, not
+        of the code object)."""
+        g = np.ascontiguousarray(geometry, dtype=np.int32).reshape(-1, 6)
+        self.nbins = [int(r[1]) for r in g]
+        self.fetched = 0                         # doubles that came to the host through fetch
+        self._create(solver, code, nconst, len(g), g.ctypes.data_as(c_int32_p), int(nconst))
+        for k, e in enumerate(edges):
+            e = _f64(e)
+            self._call("set_edges", k, _dptr(e), int(e.size))
+
+    def record(self, which, slot):
+        self._call("record", int(which), int(slot))
+
+    def pending(self, which):
+        return self._pending(int(which))
+
+    def fetch(self, which):
+        """Every row of histogram ``which`` recorded since its last fetch, ``[rows][nsys][nbins + 3]``
+        int64: the bins, then below, above and NaN (waits for the stream)."""
+        raw = self._fetch(self.nbins[which] + 3, int(which))
+        self.fetched += raw.size
+        return raw.astype(np.int64)

@@ -722,6 +722,35 @@ def lower_extrema(model, exprs, parvec_mask=0):
     return block, spec
 
 
+def lower_histograms(model, exprs, parvec_mask=0):
+    """Device histograms -> ``(block, spec)``: the C block that follows the model's own translation unit
+    (``TF_NHIST`` ... and ``tf_eval_hist``, read by csrc/tf_histogram.h; expression ``k`` is case ``k``)
+    and the constants the runtime needs.  Lowered as the other observers are (``_lower_node_expressions``):
+    the per-node values are the bits NumPy computes from the printed expressions; the host constants go
+    into the histograms' own argument buffer (``spec["host_consts"]``).  Edges, window and ``every`` are
+    not part of the block: they are data of the handle and launch arguments, and sets that differ only in
+    them share a code object.  ``TF_NHIST`` is also what makes csrc/tf_histogram.h emit its kernels: no
+    other code object holds them."""
+    lines, out, hc_list, uses_x, pars, mode = _lower_node_expressions(model, exprs, parvec_mask)
+    lines += ["    switch (k) {"]
+    lines += ["    case %d: return %s;" % (i, c) for i, c in enumerate(out)]
+    lines += ["    default: return 0.0;", "    }"]
+    block = "\n".join([
+        "// device histograms, generated by triflow_amd.codegen.lower_histograms -- do not edit",
+        "// " + " ; ".join(str(e) for e in exprs),
+        "#define TF_NHIST %d" % len(out),
+        "#define TF_NHIST_HC %d" % len(hc_list),
+        "#define TF_HIST_USES_X %d" % (1 if uses_x else 0),
+        "TF_DEVICE double tf_eval_hist(int k, const double (&w)[TF_NVAR + TF_NH][2 * TF_MP + 1], "
+        "const double* par, const double* tf_hc, double dx, double xc) {",
+        "\n".join(lines),
+        "}",
+        ""])
+    spec = dict(nhist=len(out), host_consts=hc_list, pars=pars, uses_x=int(uses_x),
+                heaviside=mode)
+    return block, spec
+
+
 def _proportional_entries(model, j_uniform, heaviside="one"):
     """Jacobian entries that are an exact power-of-two multiple of an earlier node-dependent
     entry (``-q*dxT/h`` differentiated with respect to ``T_m1`` and ``T_p1``; ``We*h*dxxxh`` with

@@ -65,16 +65,18 @@ def extra_flags(*flags):
 #: translation units of the host runtime (see the header of csrc/tf_solver.h)
 RUNTIME_SOURCES = ("tf_rt_plan.cpp", "tf_rt_io.cpp", "tf_rt_steps.cpp", "tf_rt_diag.cpp",
                    "tf_solver_sweeps.cpp", "tf_solver_linear.cpp", "tf_rt_probe.cpp", "tf_rt_record.cpp",
-                   "tf_rt_stat.cpp", "tf_rt_spectrum.cpp", "tf_rt_extrema.cpp")
+                   "tf_rt_stat.cpp", "tf_rt_spectrum.cpp", "tf_rt_extrema.cpp", "tf_rt_histogram.cpp")
 _SKELETON = ("tf_args.h", "tf_math.h", "tf_kernels.h", "tf_crs.h", "tf_coop_hip.h", "tf_cr2_hip.h", "tf_cr3_hip.h",
              "tf_cr_io.h",
              "tf_node.h", "tf_probe.h", "tf_record.h", "tf_stat.h", "tf_spectrum.h", "tf_extrema.h",
-             "tf_entry_hip.h")
+             "tf_histogram.h", "tf_entry_hip.h")
 _TU_HEAD = ('#include <hip/hip_runtime.h>\n'
             '#define TF_DEVICE __device__ __forceinline__\n'
             '%s'
             '#include "tf_math.h"\n')
 
+#: kinds of observer whose kernels are not named ``tfk_<kind>*``
+_OBSERVER_KERNELS = {"histogram": "hist"}
 _TU_TAIL = '#include "tf_kernels.h"\n#include "tf_entry_hip.h"\n'
 
 
@@ -139,7 +141,8 @@ def resource_usage(hsaco_path):
 def _compile_code_object(model, source, tag, hsaco, observer=None):
     """hipcc on the generated translation unit -> ``hsaco`` (+ source and resource table next to it).
     ``observer``: the unit carries an observer's block (build_observer_code_object) and this is its kind,
-    "probe", "record", "stat", "spectrum" or "extrema": only the kernels ``tfk_<kind>*`` of that object are ever launched, so
+    "probe", "record", "stat", "spectrum", "extrema" or "histogram" (its kernels: ``tfk_hist*``): only the kernels
+    ``tfk_<kind>*`` of that object are ever launched, so
     there is no second build for the spill gate -- one of them that spills is refused instead."""
     global BUILD_COUNT
     BUILD_COUNT += 1
@@ -166,7 +169,7 @@ def _compile_code_object(model, source, tag, hsaco, observer=None):
     usage = compile_with(flags, tmp)
     spilled = sorted(k for k, u in usage.items() if u.get("ScratchSize", 0) > 0)
     if observer:
-        spilled = [k for k in spilled if k.startswith("tfk_" + observer)]
+        spilled = [k for k in spilled if k.startswith("tfk_" + _OBSERVER_KERNELS.get(observer, observer))]
         if spilled:
             os.remove(tmp)
             raise codegen.UnsupportedExpression(
@@ -286,10 +289,12 @@ def build_code_object(model, parvec_mask=0, seg=None, sweep_block=None):
 def build_observer_code_object(model, block, kind, parvec_mask=0, seg=8, sweep_block=256):
     """The model's translation unit followed by the block of an observer of ``kind`` "probe"
     (codegen.lower_probes), "record" (codegen.lower_records), "stat" (codegen.lower_statistics),
-    "spectrum" (codegen.lower_spectra) or "extrema" (codegen.lower_extrema) -> path of the cached code object, of which only the kernels ``tfk_<kind>*`` are launched.  Same parameter
+    "spectrum" (codegen.lower_spectra), "extrema" (codegen.lower_extrema) or "histogram"
+    (codegen.lower_histograms: the one kind whose kernels, ``tfk_hist*``, no other code object holds) ->
+    path of the cached code object, of which only the kernels ``tfk_<kind>*`` are launched.  Same parameter
     layout and sweep segment as the solver's own code object: the observer's kernels read that solver's
     planes and parameter slots."""
-    if kind not in ("probe", "record", "stat", "spectrum", "extrema"):
+    if kind not in ("probe", "record", "stat", "spectrum", "extrema", "histogram"):
         raise ValueError("unknown kind of observer %r" % (kind,))
     body, _ = codegen.lower_model(model, parvec_mask=parvec_mask, seg=seg, sweep_block=sweep_block)
     source = _TU_HEAD % "" + body + block + _TU_TAIL

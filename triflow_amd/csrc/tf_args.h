@@ -469,8 +469,34 @@ struct TfExtremaArgs : TfNodeArgs {
     int* sums;                     // [nsys][nblk] extrema per workgroup
     double* ring;                  // [capacity][nsys][1 + 4 * max_count]
 };
+
+// Device histograms (tf_histogram.h, tf_rt_histogram.cpp): the distribution of the values of a model
+// expression over the window nodes start, start + step, ... < stop of every system.  Bin i counts
+// edges[i] <= v < edges[i + 1], the last bin also v == edges[nbins]; three more counters take what is
+// outside: v < edges[0], v > edges[nbins] and v != v.  A row is nbins + 3 counts, which sum to the number of
+// window nodes.  tfk_hist_partial: grid (nsys * nblk, nseg), one thread per segment of TF_PROBE_SEG nodes as
+// tfk_probe_partial, counts in unsigned 32-bit integers in LDS, one set of nbins + 3 per workgroup leaves
+// with plain stores; tfk_hist_final: grid (nsys, ceil((nbins + 3) / 64)), 1024 threads, sums the sets of its
+// system and writes row `row` of the ring as doubles (exact: a count is below 2^53).  Integers throughout: any order gives the same row.
+// These two kernels are not in the kernel table below: only a code object of kind "histogram" holds them,
+// and the runtime resolves them by name (tfb::kernel_lookup).
+#define TF_HIST_MAX_BINS 256
+struct TfHistArgs : TfNodeArgs {
+    int which;                     // expression of the histogram block (tf_eval_hist's first argument)
+    int nbins;                     // 1 ... TF_HIST_MAX_BINS
+    int nblk;                      // workgroups of tfk_hist_partial per system and segment row
+    int nseg;                      // segments of TF_PROBE_SEG nodes per chunk
+    int row;                       // row of the ring this launch writes (by value: the host counts)
+    int capacity;                  // rows of the ring
+    int start, stop, step;         // the window of nodes (slice.indices(N), step >= 1)
+    int pad;
+    const double* edges;           // [nbins + 1], finite and strictly increasing
+    unsigned* partial;             // [nsys][nseg * nblk][nbins + 3]
+    double* ring;                  // [capacity][nsys][nbins + 3]
+};
 // (passed by value to kernels of code objects the host did not compile: the bytes are the contract)
 // (the base comes first and the members follow in their order: the sizes pin the bytes)
+static_assert(sizeof(TfHistArgs) == 160, "TfHistArgs changed its layout");
 static_assert(sizeof(TfNodeArgs) == 96, "TfNodeArgs changed its layout");
 static_assert(sizeof(TfProbeArgs) == 144, "TfProbeArgs changed its layout");
 static_assert(sizeof(TfRecordArgs) == 152, "TfRecordArgs changed its layout");

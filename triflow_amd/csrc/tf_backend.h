@@ -54,6 +54,16 @@ void launch_timed(Module* m, int kernel, unsigned gx, unsigned gy, unsigned bloc
                   const void* args, size_t arg_bytes, Stream* s, Event* start, Event* stop,
                   unsigned lds_bytes = 0);
 
+// Kernels that are not in the kernel table (tf_args.h): only some code objects hold them (the device
+// histograms' "histogram" kind), so they are resolved by name once the code object is loaded and launched
+// through the handle.  kernel_lookup throws std::runtime_error when the code object has no such kernel;
+// the handle lives as long as the module.  A back end without the seam need not define either:
+// tf_rt_histogram.cpp holds weak definitions that throw "not supported by this back end".
+struct Function;
+Function* kernel_lookup(Module* m, const char* name);
+void launch_function(Function* f, unsigned gx, unsigned gy, unsigned block,
+                     const void* args, size_t arg_bytes, Stream* s);
+
 // Stream capture into an executable graph (HIP graphs): a step of a small problem is a string of
 // launch-bound kernels, replayed with one call.  The emulation has none (graphs_supported()).
 struct Graph;

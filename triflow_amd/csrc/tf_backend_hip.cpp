@@ -248,6 +248,21 @@ void launch_timed(Module* m, int kernel, unsigned gx, unsigned gy, unsigned bloc
                                     nullptr, config, start->e, stop->e, 0));
 }
 
+// (a Function* is the hipFunction_t itself: it belongs to its module)
+Function* kernel_lookup(Module* m, const char* name) {
+    hipFunction_t fn = nullptr;
+    if (hipModuleGetFunction(&fn, m->mod, name) != hipSuccess || !fn)
+        throw std::runtime_error(std::string("kernel missing from code object: ") + name);
+    return reinterpret_cast<Function*>(fn);
+}
+void launch_function(Function* f, unsigned gx, unsigned gy, unsigned block,
+                     const void* args, size_t arg_bytes, Stream* s) {
+    size_t size = arg_bytes;
+    void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, const_cast<void*>(args),
+                      HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    TF_HIP(hipModuleLaunchKernel(reinterpret_cast<hipFunction_t>(f), gx, gy, 1, block, 1, 1, 0, s->s, nullptr, config));
+}
+
 struct Graph { hipGraph_t graph; hipGraphExec_t exec; };
 bool graphs_supported() { return true; }
 void capture_begin(Stream* s) { TF_HIP(hipStreamBeginCapture(s->s, hipStreamCaptureModeThreadLocal)); }

@@ -12,6 +12,7 @@
 #include "tf_stat.h"
 #include "tf_spectrum.h"
 #include "tf_extrema.h"
+#include "tf_histogram.h"          // (tfk_hist_*: only in a code object with a histogram block)
 
 #define TF_GID ((int)(blockIdx.x * blockDim.x + threadIdx.x))
 

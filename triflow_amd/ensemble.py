@@ -107,6 +107,7 @@ class Ensemble(Observed):
                               for v in values] for e in range(self.nsys)]
         self._probes, self._recorders, self._statistics, self._spectra, self._nsteps = None, None, None, None, 0
         self._extrema = None
+        self._histograms = None
 
     def step(self, dt):
         """One fixed step of every member (asynchronous: returns after the launches)."""
@@ -136,6 +137,8 @@ class Ensemble(Observed):
             self._record_on(self._spectra)
         if self._extrema is not None:
             self._record_on(self._extrema)
+        if self._histograms is not None:
+            self._record_on(self._histograms)
 
     # ---- device probes and recorders (observers.Observed) ---------------------------------
     _n_nodes = property(lambda self: self.N)
@@ -173,6 +176,8 @@ class Ensemble(Observed):
             self._spectra.close()
         if self._extrema is not None:
             self._extrema.close()
+        if self._histograms is not None:
+            self._histograms.close()
         self.solver.close()
 
     def state(self):

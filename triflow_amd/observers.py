@@ -1,5 +1,6 @@
 """Device observers: what the probes (``probes.py``), the recorders (``recorders.py``), the statistics
-(``statistics.py``), the spectra (``spectra.py``) and the extrema (``extrema.py``) share.
+(``statistics.py``), the spectra (``spectra.py``), the extrema (``extrema.py``) and the histograms
+(``histograms.py``) share.
 
 An observer evaluates expressions in the model's own string language at the nodes of a resident state
 slot and writes one row per record into a ring in device memory.  Both kinds go through the same node
@@ -63,7 +64,7 @@ class _Bound:
 class ObserverSet:
     """The code objects and handles of a set of observers: one handle per solver the set has run on, one
     code object per parameter layout / sweep segment of those solvers.  Subclasses: ``kind`` ("probe" /
-    "record" / "stat" / "spectrum" / "extrema": ``compilers.build_observer_code_object``), ``_lower(mask) -> (block, spec)``,
+    "record" / "stat" / "spectrum" / "extrema" / "histogram": ``compilers.build_observer_code_object``), ``_lower(mask) -> (block, spec)``,
     ``_make_handle(solver, code, spec)`` and ``_flush()`` (every row still on the device to the series)."""
 
     kind = None
@@ -122,14 +123,15 @@ class ObserverSet:
 
 
 class Observed:
-    """``add_probe`` / ``add_recorder`` / ``add_statistic`` / ``add_spectrum`` / ``add_extrema`` ... of a
-    front end (``Simulation``, ``Ensemble``): reductions over space, decimated space-time pictures,
-    reductions over time, Fourier amplitudes over time and the crests and troughs over time.  The front end
+    """``add_probe`` / ``add_recorder`` / ``add_statistic`` / ``add_spectrum`` / ``add_extrema`` /
+    ``add_histogram`` ... of a front end (``Simulation``, ``Ensemble``): reductions over space, decimated
+    space-time pictures, reductions over time, Fourier amplitudes, the crests and troughs and the
+    distribution of values over time.  The front end
     has ``model``, says how a set records its current state (``_record_on(series_set)``: also called after
-    every step for ``_probes``, ``_recorders``, ``_statistics``, ``_spectra`` and ``_extrema`` that are not None), how many nodes a system has
+    every step for ``_probes``, ``_recorders``, ``_statistics``, ``_spectra``, ``_extrema`` and ``_histograms`` that are not None), how many nodes a system has
     (``_n_nodes``) and whether its series keep the axis of the systems (``_per_system``)."""
 
-    _probes = _recorders = _statistics = _spectra = _extrema = None
+    _probes = _recorders = _statistics = _spectra = _extrema = _histograms = None
     _per_system = True
 
     def _add_observer(self, series_set, name, *args):
@@ -275,3 +277,34 @@ class Observed:
         """name -> (t, n, g, x, v): float64 times, int64 counts and nodes, float64 positions and values,
         one row per recorded state."""
         return self._extrema.series(per_system=self._per_system) if self._extrema is not None else {}
+
+    # ---- device histograms (histograms.py) ------------------------------------------------
+    def add_histogram(self, name, expression, bins, range=None, every=1, nodes=slice(None), capacity=None):
+        """Record the distribution of the values ``v`` of the model expression ``expression`` at the nodes
+        ``nodes`` (a slice with a step >= 1) on the GPU (``histograms.py``).  ``bins``: an integer ``1 ...
+        histograms.MAX_BINS`` with ``range=(lo, hi)`` -- the edges are ``np.linspace(lo, hi, bins + 1)`` --
+        or a 1-D array of ``2 ... MAX_BINS + 1`` finite, strictly increasing edges (``range=None``); there
+        is no automatic range.  Bin ``i`` counts ``edges[i] <= v < edges[i + 1]``, the last bin also
+        ``v == edges[-1]``: ``np.histogram(v, bins, range)[0]``, exactly.  A row now, then after every
+        ``every``-th step (a Simulation: where the post-processes run); ``capacity``: rows of the ring in
+        device memory (default 1024).  The series is ``histograms[name] = (t, edges, counts[rows, nbins],
+        outside[rows, 3])`` with int64 counts and ``outside = (below, above, nan)`` the nodes with ``v <
+        edges[0]``, ``v > edges[-1]`` and ``v != v``: every row sums to the number of window nodes.  An
+        Ensemble's: ``counts[rows, nsys, nbins]`` and ``outside[rows, nsys, 3]``, one ``edges`` for all
+        members, of this rank's members only; the fields never come to the host for it.  Nothing is
+        accumulated over time on the device: that is ``counts.sum(0)``."""
+        if self._histograms is None:
+            from .histograms import HistogramSet
+            self._histograms = HistogramSet(self.model, self._n_nodes)
+        self._add_observer(self._histograms, name, expression, bins, range, every, nodes, capacity)
+
+    def remove_histogram(self, name):
+        if self._histograms is None:
+            raise KeyError(name)
+        self._histograms.remove(name)
+
+    @property
+    def histograms(self):
+        """name -> (t, edges, counts, outside): float64 times and edges, int64 counts, one row per
+        recorded state."""
+        return self._histograms.series(per_system=self._per_system) if self._histograms is not None else {}

@@ -109,6 +109,7 @@ class Simulation(Observed):
         self._statistics = None
         self._spectra = None
         self._extrema = None
+        self._histograms = None
         self._iterator = self.compute()
 
     def _compute_one_step(self, t, fields, pars):
@@ -149,6 +150,8 @@ class Simulation(Observed):
                     self._record_on(self._spectra)
                 if self._extrema is not None:
                     self._record_on(self._extrema)
+                if self._histograms is not None:
+                    self._record_on(self._histograms)
                 for pprocess in self.post_processes:
                     pprocess.function(self)
                 self.stream.emit(self)

@@ -251,10 +251,10 @@ def test_a_grid_of_two_nodes_is_refused_and_the_limits_are_accepted():
     es = extrema.ExtremaSet(_model("M2_diff"), 3)
     es.add("a", "U", max_count=1, capacity=1, threshold=0)
     es.add("b", "U", max_count=np.int32(8192), every=np.int64(2), threshold=np.float32(0.5), kind="min")
-    assert es._obs[0].threshold == 0.0 and es._obs[0].device_threshold() == 0.0
+    assert es._items[0].threshold == 0.0 and es._items[0].device_threshold() == 0.0
     es.add("c", "U")
     es.add("d", "U", kind="min")
-    assert es._obs[2].device_threshold() == -np.inf and es._obs[3].device_threshold() == np.inf
+    assert es._items[2].device_threshold() == -np.inf and es._items[3].device_threshold() == np.inf
 
 
 @pytest.mark.parametrize("expr", ["U *", "foo * U", "bar(U)", "dxk", 3])
@@ -316,7 +316,7 @@ def test_an_observer_that_cannot_run_is_not_kept(monkeypatch):
     sim = _sim()
     es = sim._extrema = extrema.ExtremaSet(sim.model, 50)
     es.add("kept", "U", max_count=2)
-    kept = es._obs[0]
+    kept = es._items[0]
     kept.last = kept.origin = sim.i
     kept.x = np.linspace(0, 1, 50)[None, :]
     kept.t, kept.blocks = [0.0], [np.array([[[1.0, 7.0, 0.0, 1.0, 0.0, -1.0, -1.0, -1.0, -1.0]]])]
@@ -375,7 +375,7 @@ def _fake_set():
         if solver.N != es.N:
             return extrema.ExtremaSet._bind(es, solver)
         if id(solver) not in bounds:
-            bounds[id(solver)] = extrema._Bound(_Handle(solver, [r.max_count for r in es._obs]), dict(host_consts=[]))
+            bounds[id(solver)] = extrema._Bound(_Handle(solver, [r.max_count for r in es._items]), dict(host_consts=[]))
         return bounds[id(solver)]
     es._bind = bind
     return es, bounds

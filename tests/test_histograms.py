@@ -282,14 +282,14 @@ def test_the_limits_are_accepted_and_the_edges_are_linspace():
     hs.add("b", "U", bins=np.int32(256), range=(np.float32(0.5), 3), every=np.int64(2), nodes=slice(49, None))
     hs.add("c", "U", bins=np.linspace(-1, 1, 257))
     hs.add("d", "U", bins=(0.0, 5e-324))
-    assert np.array_equal(hs._hists[0].edges, [0.0, 1.0]) and hs._hists[0].capacity == 1
-    assert hs._hists[1].edges.tobytes() == np.linspace(0.5, 3.0, 257).tobytes() and hs._hists[1].window == (49, 50, 1)
-    assert hs._hists[2].nbins == 256 and hs._hists[3].nbins == 1
-    assert hs._hists[0].edges.dtype == np.float64
+    assert np.array_equal(hs._items[0].edges, [0.0, 1.0]) and hs._items[0].capacity == 1
+    assert hs._items[1].edges.tobytes() == np.linspace(0.5, 3.0, 257).tobytes() and hs._items[1].window == (49, 50, 1)
+    assert hs._items[2].nbins == 256 and hs._items[3].nbins == 1
+    assert hs._items[0].edges.dtype == np.float64
     given = np.array([0.0, 1.0, 2.0])
     hs.add("e", "U", bins=given)
     given[1] = 5.0                                            # (the set keeps a copy)
-    assert np.array_equal(hs._hists[4].edges, [0.0, 1.0, 2.0])
+    assert np.array_equal(hs._items[4].edges, [0.0, 1.0, 2.0])
 
 
 @pytest.mark.parametrize("expr", ["U *", "foo * U", "bar(U)", "dxk", 3])
@@ -396,7 +396,7 @@ def _fake_set():
         if solver.N != hs.N:
             return histograms.HistogramSet._bind(hs, solver)
         if id(solver) not in bounds:
-            bounds[id(solver)] = histograms._Bound(_Handle(solver, [r.nbins for r in hs._hists]), dict(host_consts=[]))
+            bounds[id(solver)] = histograms._Bound(_Handle(solver, [r.nbins for r in hs._items]), dict(host_consts=[]))
         return bounds[id(solver)]
     hs._bind = bind
     return hs, bounds

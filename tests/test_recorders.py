@@ -244,7 +244,7 @@ def test_default_ring_is_sized_in_bytes_and_refuses_a_row_that_does_not_fit():
     rs.add("wide", "U")
     rs.add("thin", "U", nodes=slice(None, None, 10 ** 4))
     rs.add("fixed", "U", capacity=5)
-    wide, thin, fixed = rs._recs
+    wide, thin, fixed = rs._items
     with pytest.raises(ValueError, match="does not fit"):
         wide.rows_of_ring(1)                              # 80 MB a row
     assert thin.rows_of_ring(1) == recorders.MAX_RING_ROWS
@@ -252,7 +252,7 @@ def test_default_ring_is_sized_in_bytes_and_refuses_a_row_that_does_not_fit():
     assert fixed.rows_of_ring(1) == 4                     # (two halves of two rows)
     rs2 = recorders.RecorderSet(_model("M2_diff"), 10 ** 6)
     rs2.add("all", "U")
-    assert rs2._recs[0].rows_of_ring(1) == 4 and rs2._recs[0].rows_of_ring(1) * 8e6 <= recorders.DEFAULT_RING_BYTES
+    assert rs2._items[0].rows_of_ring(1) == 4 and rs2._items[0].rows_of_ring(1) * 8e6 <= recorders.DEFAULT_RING_BYTES
 
 
 def test_model_untouched():

@@ -208,7 +208,7 @@ def test_more_modes_than_the_tables_hold():
     assert "spectrum" in str(err.value)
     ss.add("s", "U", modes=range(MAX_MODES))
     ss.add("np", "U", modes=np.arange(3, dtype=np.int32))
-    assert ss._specs[1].modes == [0, 1, 2]
+    assert ss._items[1].modes == [0, 1, 2]
 
 
 @pytest.mark.parametrize("expr", ["U *", "foo * U", "bar(U)", "dxk", 3])
@@ -277,7 +277,7 @@ def test_spectrum_that_cannot_run_is_not_kept(monkeypatch):
     sim = _sim()
     ss = sim._spectra = spectra.SpectrumSet(sim.model, 50)
     ss.add("kept", "U", modes=[0, 1])
-    kept = ss._specs[0]
+    kept = ss._items[0]
     kept.last = kept.origin = sim.i
     kept.t, kept.blocks, kept.k = [0.0], [np.arange(2.0).reshape(1, 1, 2).astype(np.complex128)], np.array([0.0, 1.0])
     monkeypatch.setattr(spectra.SpectrumSet, "_bind", fail)
@@ -330,7 +330,7 @@ def _fake_set():
         if solver.N != ss.N:
             return spectra.SpectrumSet._bind(ss, solver)
         if id(solver) not in bounds:
-            bounds[id(solver)] = spectra._Bound(_Handle(solver, [len(r.modes) for r in ss._specs]), dict(host_consts=[]))
+            bounds[id(solver)] = spectra._Bound(_Handle(solver, [len(r.modes) for r in ss._items]), dict(host_consts=[]))
         return bounds[id(solver)]
     ss._bind = bind
     return ss, bounds
@@ -397,13 +397,13 @@ def test_ensemble_wavenumbers_follow_the_recorders_rule_for_x():
     ss.add("m", "U", modes=[0, 3])
     x = np.linspace(0, 1, 50)
     ss.record(Eight(), 0, 0.0, 0, np.tile(x, (8, 1)), [[1.0]] * 8)
-    ss._specs[0].pending.clear()
+    ss._items[0].pending.clear()
     assert ss.series()["m"][1].shape == (2,)
     ss2, _ = _fake_set()
     ss2.add("m", "U", modes=[0, 3])
     xs = np.array([x * (1 + e) for e in range(8)])
     ss2.record(Eight(), 0, 0.0, 0, xs, [[1.0]] * 8)
-    ss2._specs[0].pending.clear()
+    ss2._items[0].pending.clear()
     k = ss2.series()["m"][1]
     assert k.shape == (8, 2) and np.allclose(k[:, 1] * (1 + np.arange(8)), k[0, 1])
     assert ss2.series(per_system=False)["m"][1].shape == (2,)

@@ -306,7 +306,7 @@ def test_statistic_that_cannot_run_is_not_kept(monkeypatch):
     sim = _sim()
     rs = sim._statistics = statistics.StatisticSet(sim.model, 50)
     rs.add("kept", "U", stat="max")
-    kept = rs._stats[0]
+    kept = rs._items[0]
     kept.n, kept.last, kept.origin, kept.held = 3, sim.i, sim.i, np.arange(50.0).reshape(1, 1, 50)
     monkeypatch.setattr(statistics.StatisticSet, "_bind", fail)
     with pytest.raises(UnsupportedExpression):

@@ -630,7 +630,27 @@ class DeviceProbe(_DeviceObserver):
         return self._fetch(self.nprobe)
 
 
-class DeviceRecord(_DeviceObserver):
+class _DeviceRows(_DeviceObserver):
+    """What ``tf_record``, ``tf_spectrum``, ``tf_extrema`` and ``tf_histogram`` share besides: a ring of rows
+    per item ``which`` of the set.  A subclass shapes the rows of ``_fetch_rows`` in its ``fetch``."""
+
+    fetched = 0                                  # doubles that came to the host through fetch
+
+    def record(self, which, slot):
+        self._call("record", int(which), int(slot))
+
+    def pending(self, which):
+        return self._pending(int(which))
+
+    def _fetch_rows(self, which, ncols):
+        """Every row of item ``which`` recorded since its last fetch, ``[rows][nsys][ncols]`` doubles
+        (waits for the stream)."""
+        raw = self._fetch(ncols, int(which))
+        self.fetched += raw.size
+        return raw
+
+
+class DeviceRecord(_DeviceRows):
     """``tf_record``: the record kernel of one recorder set bound to one solver, and the rings."""
 
     _prefix, _noun = "tf_record", "recorder"
@@ -641,15 +661,9 @@ class DeviceRecord(_DeviceObserver):
         self.ncols = [-(-(int(r[3]) - int(r[2])) // int(r[4])) for r in g]
         self._create(solver, code, nconst, len(g), g.ctypes.data_as(c_int32_p), int(nconst))
 
-    def record(self, which, slot):
-        self._call("record", int(which), int(slot))
-
-    def pending(self, which):
-        return self._pending(int(which))
-
     def fetch(self, which):
         """Every row of recorder ``which`` recorded since its last fetch, ``[rows][nsys][ncols]``."""
-        return self._fetch(self.ncols[which], int(which))
+        return self._fetch_rows(which, self.ncols[which])
 
 
 class DeviceStat(_DeviceObserver):
@@ -684,7 +698,7 @@ class DeviceStat(_DeviceObserver):
         self._call("load", int(which), _dptr(a))
 
 
-class DeviceSpectrum(_DeviceObserver):
+class DeviceSpectrum(_DeviceRows):
     """``tf_spectrum``: the spectrum kernels of one spectrum set bound to one solver, the modes and the
     rings."""
 
@@ -695,27 +709,18 @@ class DeviceSpectrum(_DeviceObserver):
         spectrum, its modes (uploaded here: they are data of the handle, not of the code object)."""
         g = np.ascontiguousarray(geometry, dtype=np.int32).reshape(-1, 3)
         self.nmodes = [int(r[1]) for r in g]
-        self.fetched = 0                         # doubles that came to the host through fetch
         self._create(solver, code, nconst, len(g), g.ctypes.data_as(c_int32_p), int(nconst))
         for k, m in enumerate(modes):
             m = np.ascontiguousarray(m, dtype=np.int32)
             self._call("set_modes", k, m.ctypes.data_as(c_int32_p), int(m.size))
 
-    def record(self, which, slot):
-        self._call("record", int(which), int(slot))
-
-    def pending(self, which):
-        return self._pending(int(which))
-
     def fetch(self, which):
         """Every row of spectrum ``which`` recorded since its last fetch, ``[rows][nsys][nmodes]``
         complex128 (waits for the stream)."""
-        raw = self._fetch(2 * self.nmodes[which], int(which))
-        self.fetched += raw.size
-        return np.ascontiguousarray(raw).view(np.complex128)
+        return np.ascontiguousarray(self._fetch_rows(which, 2 * self.nmodes[which])).view(np.complex128)
 
 
-class DeviceExtrema(_DeviceObserver):
+class DeviceExtrema(_DeviceRows):
     """``tf_extrema``: the extrema kernels of one extrema set bound to one solver, and the rings."""
 
     _prefix, _noun = "tf_extrema", "extrema"
@@ -726,24 +731,15 @@ class DeviceExtrema(_DeviceObserver):
         g = np.ascontiguousarray(geometry, dtype=np.int32).reshape(-1, 4)
         th = _f64(thresholds).reshape(len(g))
         self.max_count = [int(r[2]) for r in g]
-        self.fetched = 0                         # doubles that came to the host through fetch
         self._create(solver, code, nconst, len(g), g.ctypes.data_as(c_int32_p), _dptr(th), int(nconst))
-
-    def record(self, which, slot):
-        self._call("record", int(which), int(slot))
-
-    def pending(self, which):
-        return self._pending(int(which))
 
     def fetch(self, which):
         """Every row of observer ``which`` recorded since its last fetch, ``[rows][nsys][1 + 4 * max_count]``:
         the count, then ``(g, v[g-1], v[g], v[g+1])`` per entry (waits for the stream)."""
-        raw = self._fetch(1 + 4 * self.max_count[which], int(which))
-        self.fetched += raw.size
-        return raw
+        return self._fetch_rows(which, 1 + 4 * self.max_count[which])
 
 
-class DeviceHistogram(_DeviceObserver):
+class DeviceHistogram(_DeviceRows):
     """``tf_histogram``: the histogram kernels of one histogram set bound to one solver, the edges and the
     rings."""
 
@@ -755,21 +751,12 @@ class DeviceHistogram(_DeviceObserver):
         of the code object)."""
         g = np.ascontiguousarray(geometry, dtype=np.int32).reshape(-1, 6)
         self.nbins = [int(r[1]) for r in g]
-        self.fetched = 0                         # doubles that came to the host through fetch
         self._create(solver, code, nconst, len(g), g.ctypes.data_as(c_int32_p), int(nconst))
         for k, e in enumerate(edges):
             e = _f64(e)
             self._call("set_edges", k, _dptr(e), int(e.size))
 
-    def record(self, which, slot):
-        self._call("record", int(which), int(slot))
-
-    def pending(self, which):
-        return self._pending(int(which))
-
     def fetch(self, which):
         """Every row of histogram ``which`` recorded since its last fetch, ``[rows][nsys][nbins + 3]``
         int64: the bins, then below, above and NaN (waits for the stream)."""
-        raw = self._fetch(self.nbins[which] + 3, int(which))
-        self.fetched += raw.size
-        return raw.astype(np.int64)
+        return self._fetch_rows(which, self.nbins[which] + 3).astype(np.int64)

@@ -615,30 +615,38 @@ def lower_probes(model, exprs, reductions, parvec_mask=0):
 RECORD_POOLS = ("sample", "max", "min", "mean")
 
 
+def _lower_switch(model, exprs, parvec_mask, stem, eval_name, count_key, words, wrapper):
+    """The ``switch (k)`` block of the observers that evaluate one expression per call -> ``(block,
+    spec)``: ``TF_N<stem>``, ``TF_N<stem>_HC``, ``TF_<stem>_USES_X`` (one stem serves the counts and the
+    uses-x macro of every kind) and ``<eval_name>``, expression ``k`` being case ``k``;
+    ``spec[count_key]`` counts the expressions.  ``words`` and ``wrapper``: the kind and the public
+    function the header comment names."""
+    lines, out, hc_list, uses_x, pars, mode = _lower_node_expressions(model, exprs, parvec_mask)
+    lines += ["    switch (k) {"]
+    lines += ["    case %d: return %s;" % (i, c) for i, c in enumerate(out)]
+    lines += ["    default: return 0.0;", "    }"]
+    block = "\n".join([
+        "// %s, generated by triflow_amd.codegen.%s -- do not edit" % (words, wrapper),
+        "// " + " ; ".join(str(e) for e in exprs),
+        "#define TF_N%s %d" % (stem, len(out)),
+        "#define TF_N%s_HC %d" % (stem, len(hc_list)),
+        "#define TF_%s_USES_X %d" % (stem, 1 if uses_x else 0),
+        "TF_DEVICE double %s(int k, const double (&w)[TF_NVAR + TF_NH][2 * TF_MP + 1], "
+        "const double* par, const double* tf_hc, double dx, double xc) {" % eval_name,
+        "\n".join(lines),
+        "}",
+        ""])
+    spec = {count_key: len(out), "host_consts": hc_list, "pars": pars, "uses_x": int(uses_x), "heaviside": mode}
+    return block, spec
+
+
 def lower_records(model, exprs, parvec_mask=0):
     """Device recorders -> ``(block, spec)``: the C block that follows the model's own translation unit
     (``TF_NREC`` ... and ``tf_eval_record``, read by csrc/tf_record.h; expression ``k`` is case ``k``)
     and the constants the runtime needs.  Lowered as the probes are (``_lower_node_expressions``): the
     per-node values are the bits NumPy computes from the printed expressions; the host constants go
     into the recorders' own argument buffer (``spec["host_consts"]``)."""
-    lines, out, hc_list, uses_x, pars, mode = _lower_node_expressions(model, exprs, parvec_mask)
-    lines += ["    switch (k) {"]
-    lines += ["    case %d: return %s;" % (i, c) for i, c in enumerate(out)]
-    lines += ["    default: return 0.0;", "    }"]
-    block = "\n".join([
-        "// device recorders, generated by triflow_amd.codegen.lower_records -- do not edit",
-        "// " + " ; ".join(str(e) for e in exprs),
-        "#define TF_NREC %d" % len(out),
-        "#define TF_NREC_HC %d" % len(hc_list),
-        "#define TF_REC_USES_X %d" % (1 if uses_x else 0),
-        "TF_DEVICE double tf_eval_record(int k, const double (&w)[TF_NVAR + TF_NH][2 * TF_MP + 1], "
-        "const double* par, const double* tf_hc, double dx, double xc) {",
-        "\n".join(lines),
-        "}",
-        ""])
-    spec = dict(nrec=len(out), host_consts=hc_list, pars=pars, uses_x=int(uses_x),
-                heaviside=mode)
-    return block, spec
+    return _lower_switch(model, exprs, parvec_mask, "REC", "tf_eval_record", "nrec", "device recorders", "lower_records")
 
 
 def lower_statistics(model, exprs, parvec_mask=0):
@@ -647,24 +655,7 @@ def lower_statistics(model, exprs, parvec_mask=0):
     the constants the runtime needs.  Lowered as the probes and the recorders are
     (``_lower_node_expressions``): the per-node values are the bits NumPy computes from the printed
     expressions; the host constants go into the statistics' own argument buffer (``spec["host_consts"]``)."""
-    lines, out, hc_list, uses_x, pars, mode = _lower_node_expressions(model, exprs, parvec_mask)
-    lines += ["    switch (k) {"]
-    lines += ["    case %d: return %s;" % (i, c) for i, c in enumerate(out)]
-    lines += ["    default: return 0.0;", "    }"]
-    block = "\n".join([
-        "// device statistics, generated by triflow_amd.codegen.lower_statistics -- do not edit",
-        "// " + " ; ".join(str(e) for e in exprs),
-        "#define TF_NSTAT %d" % len(out),
-        "#define TF_NSTAT_HC %d" % len(hc_list),
-        "#define TF_STAT_USES_X %d" % (1 if uses_x else 0),
-        "TF_DEVICE double tf_eval_stat(int k, const double (&w)[TF_NVAR + TF_NH][2 * TF_MP + 1], "
-        "const double* par, const double* tf_hc, double dx, double xc) {",
-        "\n".join(lines),
-        "}",
-        ""])
-    spec = dict(nstat=len(out), host_consts=hc_list, pars=pars, uses_x=int(uses_x),
-                heaviside=mode)
-    return block, spec
+    return _lower_switch(model, exprs, parvec_mask, "STAT", "tf_eval_stat", "nstat", "device statistics", "lower_statistics")
 
 
 def lower_spectra(model, exprs, parvec_mask=0):
@@ -674,24 +665,7 @@ def lower_spectra(model, exprs, parvec_mask=0):
     the per-node values are the bits NumPy computes from the printed expressions; the host constants go
     into the spectra's own argument buffer (``spec["host_consts"]``).  The modes are not part of the
     block: spectra of the same expressions share a code object whatever their modes."""
-    lines, out, hc_list, uses_x, pars, mode = _lower_node_expressions(model, exprs, parvec_mask)
-    lines += ["    switch (k) {"]
-    lines += ["    case %d: return %s;" % (i, c) for i, c in enumerate(out)]
-    lines += ["    default: return 0.0;", "    }"]
-    block = "\n".join([
-        "// device spectra, generated by triflow_amd.codegen.lower_spectra -- do not edit",
-        "// " + " ; ".join(str(e) for e in exprs),
-        "#define TF_NSPEC %d" % len(out),
-        "#define TF_NSPEC_HC %d" % len(hc_list),
-        "#define TF_SPEC_USES_X %d" % (1 if uses_x else 0),
-        "TF_DEVICE double tf_eval_spectrum(int k, const double (&w)[TF_NVAR + TF_NH][2 * TF_MP + 1], "
-        "const double* par, const double* tf_hc, double dx, double xc) {",
-        "\n".join(lines),
-        "}",
-        ""])
-    spec = dict(nspec=len(out), host_consts=hc_list, pars=pars, uses_x=int(uses_x),
-                heaviside=mode)
-    return block, spec
+    return _lower_switch(model, exprs, parvec_mask, "SPEC", "tf_eval_spectrum", "nspec", "device spectra", "lower_spectra")
 
 
 def lower_extrema(model, exprs, parvec_mask=0):
@@ -702,24 +676,7 @@ def lower_extrema(model, exprs, parvec_mask=0):
     into the extrema's own argument buffer (``spec["host_consts"]``).  Kind, threshold, ``max_count`` and
     ``every`` are not part of the block: they are launch arguments, and sets that differ only in them
     share a code object."""
-    lines, out, hc_list, uses_x, pars, mode = _lower_node_expressions(model, exprs, parvec_mask)
-    lines += ["    switch (k) {"]
-    lines += ["    case %d: return %s;" % (i, c) for i, c in enumerate(out)]
-    lines += ["    default: return 0.0;", "    }"]
-    block = "\n".join([
-        "// device extrema, generated by triflow_amd.codegen.lower_extrema -- do not edit",
-        "// " + " ; ".join(str(e) for e in exprs),
-        "#define TF_NEXT %d" % len(out),
-        "#define TF_NEXT_HC %d" % len(hc_list),
-        "#define TF_EXT_USES_X %d" % (1 if uses_x else 0),
-        "TF_DEVICE double tf_eval_extrema(int k, const double (&w)[TF_NVAR + TF_NH][2 * TF_MP + 1], "
-        "const double* par, const double* tf_hc, double dx, double xc) {",
-        "\n".join(lines),
-        "}",
-        ""])
-    spec = dict(next=len(out), host_consts=hc_list, pars=pars, uses_x=int(uses_x),
-                heaviside=mode)
-    return block, spec
+    return _lower_switch(model, exprs, parvec_mask, "EXT", "tf_eval_extrema", "next", "device extrema", "lower_extrema")
 
 
 def lower_histograms(model, exprs, parvec_mask=0):
@@ -731,24 +688,7 @@ def lower_histograms(model, exprs, parvec_mask=0):
     not part of the block: they are data of the handle and launch arguments, and sets that differ only in
     them share a code object.  ``TF_NHIST`` is also what makes csrc/tf_histogram.h emit its kernels: no
     other code object holds them."""
-    lines, out, hc_list, uses_x, pars, mode = _lower_node_expressions(model, exprs, parvec_mask)
-    lines += ["    switch (k) {"]
-    lines += ["    case %d: return %s;" % (i, c) for i, c in enumerate(out)]
-    lines += ["    default: return 0.0;", "    }"]
-    block = "\n".join([
-        "// device histograms, generated by triflow_amd.codegen.lower_histograms -- do not edit",
-        "// " + " ; ".join(str(e) for e in exprs),
-        "#define TF_NHIST %d" % len(out),
-        "#define TF_NHIST_HC %d" % len(hc_list),
-        "#define TF_HIST_USES_X %d" % (1 if uses_x else 0),
-        "TF_DEVICE double tf_eval_hist(int k, const double (&w)[TF_NVAR + TF_NH][2 * TF_MP + 1], "
-        "const double* par, const double* tf_hc, double dx, double xc) {",
-        "\n".join(lines),
-        "}",
-        ""])
-    spec = dict(nhist=len(out), host_consts=hc_list, pars=pars, uses_x=int(uses_x),
-                heaviside=mode)
-    return block, spec
+    return _lower_switch(model, exprs, parvec_mask, "HIST", "tf_eval_hist", "nhist", "device histograms", "lower_histograms")
 
 
 def _proportional_entries(model, j_uniform, heaviside="one"):

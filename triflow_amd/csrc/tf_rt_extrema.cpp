@@ -4,10 +4,8 @@
 // solver's stream, on one of its state slots (tf_observer, tf_solver.h: what the extrema share with the
 // other observers): the two launches per observer that is due, one row [nsys][1 + 4 * max_count] per record.
 //
-// An observer owns the counts of its chunks and workgroups (integers) and a ring of `capacity` rows in
-// device memory.  The host counts the rows and hands the row index to the kernels by value, as the spectra
-// do: nothing of the ring's state lives on the device, and a record never waits.  The host waits only when
-// the ring is full (one copy of all of it before the next record) and when the caller fetches.
+// An observer owns the counts of its chunks and workgroups (integers) and a ring of rows in device
+// memory, counted on the host (RowRing, tf_solver.h).
 #include "tf_solver.h"
 
 namespace {
@@ -15,28 +13,16 @@ namespace {
 const size_t kDefaultRows = 1024, kDefaultBytes = (size_t)32 << 20;
 
 struct Extrema {
-    int expr = 0, kind = 0, max_count = 0, capacity = 0;
+    int expr = 0, kind = 0, max_count = 0;
     double threshold = 0.0;
-    size_t row = 0;                            // doubles of one row: nsys * (1 + 4 * max_count)
-    DevBuf counts, sums, ring;                 // counts, sums: int32 in buffers of doubles
-    int on_device = 0;                         // rows in the ring (the next record writes this row)
-    std::vector<double> rows;                  // drained, not fetched yet
+    DevBuf counts, sums;                       // int32 in buffers of doubles
+    RowRing ring;                              // a row: nsys * (1 + 4 * max_count) doubles
 };
 }  // namespace
 
 struct tf_extrema : tf_observer {
     int nblk = 0;
     std::vector<std::unique_ptr<Extrema>> obs;
-
-    // the ring's rows to ex.rows, one copy (waits for the stream); the next record writes row 0
-    void drain(Extrema& ex) {
-        if (ex.on_device == 0) return;
-        const size_t n = (size_t)ex.on_device * ex.row;
-        const size_t at = ex.rows.size();
-        ex.rows.resize(at + n);
-        tfb::d2h(ex.rows.data() + at, ex.ring.p, n * sizeof(double), solver->stream);
-        ex.on_device = 0;
-    }
 };
 
 extern "C" {
@@ -49,29 +35,25 @@ int tf_extrema_create(tf_solver* s, const void* code_object, size_t code_size, i
     require(nconst >= 0, "tf_extrema_create: bad constant count");
     require(s->L1.N >= 3, "tf_extrema_create: an extremum has two neighbours, a system three nodes at least");
     std::unique_ptr<tf_extrema> p(new tf_extrema());
-    // The expressions of the block are numbered in the order the observers first use them
-    // (ExtremaSet.expressions): an observer names one that an earlier one named, or the next one.
-    // So no index passes that is not a case of tf_eval_extrema in a block lowered from the same set.
     int nexpr = 0;
     for (int k = 0; k < next; ++k) {
         const int32_t* g = geometry + 4 * k;
         p->obs.emplace_back(new Extrema());
         Extrema& ex = *p->obs[k];
-        ex.expr = g[0]; ex.kind = g[1]; ex.max_count = g[2]; ex.capacity = g[3];
+        ex.expr = g[0]; ex.kind = g[1]; ex.max_count = g[2]; ex.ring.capacity = g[3];
         ex.threshold = thresholds[k];
-        require(ex.expr >= 0 && ex.expr <= nexpr,
-                "tf_extrema_create: expressions are numbered in the order the observers first use them");
-        nexpr = std::max(nexpr, ex.expr + 1);
+        tf_observer::require_numbered_in_order(
+            ex.expr, nexpr, "tf_extrema_create: expressions are numbered in the order the observers first use them");
         require(ex.kind == TF_EXT_MAX || ex.kind == TF_EXT_MIN, "tf_extrema_create: kind is max (0) or min (1)");
         require(ex.max_count >= 1 && ex.max_count <= TF_EXT_MAX_COUNT, "tf_extrema_create: max_count is 1 ... 8192");
-        require(ex.capacity >= 0, "tf_extrema_create: a ring has one row at least (0: the default)");
+        require(ex.ring.capacity >= 0, "tf_extrema_create: a ring has one row at least (0: the default)");
         require(ex.threshold == ex.threshold, "tf_extrema_create: the threshold is a NaN");
-        ex.row = (size_t)s->nsys * (1 + 4 * (size_t)ex.max_count);
-        if (ex.capacity == 0) {
-            const size_t fit = kDefaultBytes / (ex.row * sizeof(double));
+        ex.ring.row = (size_t)s->nsys * (1 + 4 * (size_t)ex.max_count);
+        if (ex.ring.capacity == 0) {
+            const size_t fit = kDefaultBytes / (ex.ring.row * sizeof(double));
             require(fit >= 1, "tf_extrema_create: one row of the ring (8 * nsys * (1 + 4 * max_count) bytes) is "
                               "more than the 32 MB of a default ring: a smaller max_count, or a capacity");
-            ex.capacity = (int)std::min(fit, kDefaultRows);
+            ex.ring.capacity = (int)std::min(fit, kDefaultRows);
         }
     }
     p->init(s, code_object, code_size, nconst);
@@ -80,7 +62,7 @@ int tf_extrema_create(tf_solver* s, const void* code_object, size_t code_size, i
         Extrema& ex = *exp;
         ex.counts.alloc(((size_t)s->nsys * p->nblk * 256 + 1) / 2, p->bytes);
         ex.sums.alloc(((size_t)s->nsys * p->nblk + 1) / 2, p->bytes);
-        ex.ring.alloc((size_t)ex.capacity * ex.row, p->bytes);
+        ex.ring.alloc(p->bytes);
     }
     *out = p.release();
     TF_API_END
@@ -108,7 +90,7 @@ int tf_extrema_record(tf_extrema* p, int32_t which, int32_t slot) {
     require(which >= 0 && which < (int)p->obs.size(), "tf_extrema_record: no such observer");
     tf_solver* s = p->solver;
     Extrema& ex = *p->obs[which];
-    if (ex.on_device == ex.capacity) p->drain(ex);
+    const int row = ex.ring.next_row(s->stream);
     TfExtremaArgs a;
     std::memset(&a, 0, sizeof a);
     static_cast<TfNodeArgs&>(a) = p->node_args(slot);
@@ -116,15 +98,15 @@ int tf_extrema_record(tf_extrema* p, int32_t which, int32_t slot) {
     a.kind = ex.kind;
     a.max_count = ex.max_count;
     a.nblk = p->nblk;
-    a.row = ex.on_device;
-    a.capacity = ex.capacity;
+    a.row = row;
+    a.capacity = ex.ring.capacity;
     a.threshold = ex.threshold;
     a.counts = (int*)ex.counts.p;
     a.sums = (int*)ex.sums.p;
-    a.ring = ex.ring.p;
+    a.ring = ex.ring.ring.p;
     p->launch(TFK_EXTREMA_COUNT, (unsigned)(s->nsys * p->nblk), 1, 256, &a, sizeof a);
     p->launch(TFK_EXTREMA_WRITE, (unsigned)(s->nsys * p->nblk), 1, 256, &a, sizeof a);
-    ++ex.on_device;
+    ++ex.ring.on_device;
     TF_API_END
 }
 
@@ -132,13 +114,7 @@ int tf_extrema_fetch(tf_extrema* p, int32_t which, double* out, int64_t max_rows
     TF_API_BEGIN
     require(p && rows && (out || max_rows == 0), "null argument");
     require(which >= 0 && which < (int)p->obs.size(), "tf_extrema_fetch: no such observer");
-    Extrema& ex = *p->obs[which];
-    p->drain(ex);
-    const int64_t have = (int64_t)(ex.rows.size() / ex.row);
-    const int64_t n = std::min<int64_t>(have, std::max<int64_t>(max_rows, 0));
-    if (n) std::memcpy(out, ex.rows.data(), (size_t)n * ex.row * sizeof(double));
-    ex.rows.erase(ex.rows.begin(), ex.rows.begin() + (size_t)n * ex.row);
-    *rows = n;
+    p->obs[which]->ring.fetch(p->solver->stream, out, max_rows, rows);
     TF_API_END
 }
 
@@ -146,8 +122,7 @@ int tf_extrema_pending(tf_extrema* p, int32_t which, int64_t* rows) {
     TF_API_BEGIN
     require(p && rows, "null argument");
     require(which >= 0 && which < (int)p->obs.size(), "tf_extrema_pending: no such observer");
-    const Extrema& ex = *p->obs[which];
-    *rows = ex.on_device + (int64_t)(ex.rows.size() / ex.row);
+    *rows = p->obs[which]->ring.pending();
     TF_API_END
 }
 

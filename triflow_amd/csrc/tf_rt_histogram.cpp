@@ -11,10 +11,7 @@
 // line in tf_timing_get: a kernel trace times them.
 //
 // A histogram owns its edges (a device buffer: the code object does not know them), the counts of its
-// workgroups and a ring of `capacity` rows in device memory.  The host counts the rows and hands the row
-// index to the kernels by value, as the spectra do: nothing of the ring's state lives on the device, and a
-// record never waits.  The host waits only when the ring is full (one copy of all of it before the next
-// record) and when the caller fetches.
+// workgroups and a ring of rows in device memory, counted on the host (RowRing, tf_solver.h).
 #include "tf_solver.h"
 
 #include <cmath>
@@ -32,12 +29,10 @@ __attribute__((weak)) void launch_function(Function*, unsigned, unsigned, unsign
 
 namespace {
 struct Histogram {
-    int expr = 0, nbins = 0, capacity = 0, start = 0, stop = 0, step = 1;
+    int expr = 0, nbins = 0, start = 0, stop = 0, step = 1;
     bool have_edges = false;
-    size_t row = 0;                            // doubles of one row: nsys * (nbins + 3)
-    DevBuf edges, partial, ring;               // partial: uint32 [nsys][nseg * nblk][nbins + 3] in a buffer of doubles
-    int on_device = 0;                         // rows in the ring (the next record writes this row)
-    std::vector<double> rows;                  // drained, not fetched yet
+    DevBuf edges, partial;                     // partial: uint32 [nsys][nseg * nblk][nbins + 3] in a buffer of doubles
+    RowRing ring;                              // a row: nsys * (nbins + 3) doubles
 };
 }  // namespace
 
@@ -46,16 +41,6 @@ struct tf_histogram : tf_observer {
     tfb::Function* fn_partial = nullptr;     // tfk_hist_partial, tfk_hist_final of the set's code object
     tfb::Function* fn_final = nullptr;
     std::vector<std::unique_ptr<Histogram>> hists;
-
-    // the ring's rows to h.rows, one copy (waits for the stream); the next record writes row 0
-    void drain(Histogram& h) {
-        if (h.on_device == 0) return;
-        const size_t n = (size_t)h.on_device * h.row;
-        const size_t at = h.rows.size();
-        h.rows.resize(at + n);
-        tfb::d2h(h.rows.data() + at, h.ring.p, n * sizeof(double), solver->stream);
-        h.on_device = 0;
-    }
 };
 
 extern "C" {
@@ -67,21 +52,17 @@ int tf_histogram_create(tf_solver* s, const void* code_object, size_t code_size,
     require(nhist >= 1 && nhist <= 64, "tf_histogram_create: 1 ... 64 histograms");
     require(nconst >= 0, "tf_histogram_create: bad constant count");
     std::unique_ptr<tf_histogram> p(new tf_histogram());
-    // The expressions of the block are numbered in the order the histograms first use them
-    // (HistogramSet.expressions): a histogram names one that an earlier histogram named, or the next one.
-    // So no index passes that is not a case of tf_eval_hist in a block lowered from the same set.
     int nexpr = 0;
     const int N = s->L1.N;
     for (int k = 0; k < nhist; ++k) {
         const int32_t* g = geometry + 6 * k;
         p->hists.emplace_back(new Histogram());
         Histogram& h = *p->hists[k];
-        h.expr = g[0]; h.nbins = g[1]; h.capacity = g[2]; h.start = g[3]; h.stop = g[4]; h.step = g[5];
-        require(h.expr >= 0 && h.expr <= nexpr,
-                "tf_histogram_create: expressions are numbered in the order the histograms first use them");
-        nexpr = std::max(nexpr, h.expr + 1);
+        h.expr = g[0]; h.nbins = g[1]; h.ring.capacity = g[2]; h.start = g[3]; h.stop = g[4]; h.step = g[5];
+        tf_observer::require_numbered_in_order(
+            h.expr, nexpr, "tf_histogram_create: expressions are numbered in the order the histograms first use them");
         require(h.nbins >= 1 && h.nbins <= TF_HIST_MAX_BINS, "tf_histogram_create: 1 ... 256 bins per histogram");
-        require(h.capacity >= 1, "tf_histogram_create: a ring has one row at least");
+        require(h.ring.capacity >= 1, "tf_histogram_create: a ring has one row at least");
         require(h.step >= 1 && h.start >= 0 && h.start <= N && h.stop >= 0 && h.stop <= N,
                 "tf_histogram_create: the window is slice.indices(N) with a step >= 1");
     }
@@ -92,10 +73,10 @@ int tf_histogram_create(tf_solver* s, const void* code_object, size_t code_size,
     p->nseg = (int)tf_solver::cdiv(s->L1.M, TF_PROBE_SEG);
     for (auto& hp : p->hists) {
         Histogram& h = *hp;
-        h.row = (size_t)s->nsys * (h.nbins + 3);
+        h.ring.row = (size_t)s->nsys * (h.nbins + 3);
         h.edges.alloc((size_t)h.nbins + 1, p->bytes);
         h.partial.alloc(((size_t)s->nsys * p->nseg * p->nblk * (h.nbins + 3) + 1) / 2, p->bytes);
-        h.ring.alloc((size_t)h.capacity * h.row, p->bytes);
+        h.ring.alloc(p->bytes);
     }
     *out = p.release();
     TF_API_END
@@ -139,7 +120,7 @@ int tf_histogram_record(tf_histogram* p, int32_t which, int32_t slot) {
     tf_solver* s = p->solver;
     Histogram& h = *p->hists[which];
     require(h.have_edges, "tf_histogram_record: set_edges first");
-    if (h.on_device == h.capacity) p->drain(h);
+    const int row = h.ring.next_row(s->stream);
     TfHistArgs a;
     std::memset(&a, 0, sizeof a);
     static_cast<TfNodeArgs&>(a) = p->node_args(slot);
@@ -147,17 +128,17 @@ int tf_histogram_record(tf_histogram* p, int32_t which, int32_t slot) {
     a.nbins = h.nbins;
     a.nblk = p->nblk;
     a.nseg = p->nseg;
-    a.row = h.on_device;
-    a.capacity = h.capacity;
+    a.row = row;
+    a.capacity = h.ring.capacity;
     a.start = h.start; a.stop = h.stop; a.step = h.step;
     a.edges = h.edges.p;
     a.partial = (unsigned*)h.partial.p;
-    a.ring = h.ring.p;
+    a.ring = h.ring.ring.p;
     tfb::launch_function(p->fn_partial, (unsigned)(s->nsys * p->nblk), (unsigned)p->nseg, 256, &a, sizeof a, s->stream);
     // (TF_HIST_FINAL_BLOCK of tf_histogram.h: 16 wavefronts over 64 counters each)
     tfb::launch_function(p->fn_final, (unsigned)s->nsys, (unsigned)tf_solver::cdiv(h.nbins + 3, 64), 1024, &a, sizeof a,
                          s->stream);
-    ++h.on_device;
+    ++h.ring.on_device;
     TF_API_END
 }
 
@@ -165,13 +146,7 @@ int tf_histogram_fetch(tf_histogram* p, int32_t which, double* out, int64_t max_
     TF_API_BEGIN
     require(p && rows && (out || max_rows == 0), "null argument");
     require(which >= 0 && which < (int)p->hists.size(), "tf_histogram_fetch: no such histogram");
-    Histogram& h = *p->hists[which];
-    p->drain(h);
-    const int64_t have = (int64_t)(h.rows.size() / h.row);
-    const int64_t n = std::min<int64_t>(have, std::max<int64_t>(max_rows, 0));
-    if (n) std::memcpy(out, h.rows.data(), (size_t)n * h.row * sizeof(double));
-    h.rows.erase(h.rows.begin(), h.rows.begin() + (size_t)n * h.row);
-    *rows = n;
+    p->hists[which]->ring.fetch(p->solver->stream, out, max_rows, rows);
     TF_API_END
 }
 
@@ -179,8 +154,7 @@ int tf_histogram_pending(tf_histogram* p, int32_t which, int64_t* rows) {
     TF_API_BEGIN
     require(p && rows, "null argument");
     require(which >= 0 && which < (int)p->hists.size(), "tf_histogram_pending: no such histogram");
-    const Histogram& h = *p->hists[which];
-    *rows = h.on_device + (int64_t)(h.rows.size() / h.row);
+    *rows = p->hists[which]->ring.pending();
     TF_API_END
 }
 

@@ -6,35 +6,20 @@
 // per record.
 //
 // A spectrum owns its modes (a device buffer: the code object does not know them), the partials of its
-// workgroups and a ring of `capacity` rows in device memory.  The host counts the rows and hands the row
-// index to the kernels by value, as the statistics hand over their sample count: nothing of the ring's
-// state lives on the device, and a record never waits.  The host waits only when the ring is full (one
-// copy of all of it before the next record) and when the caller fetches.
+// workgroups and a ring of rows in device memory, counted on the host (RowRing, tf_solver.h).
 #include "tf_solver.h"
 
 namespace {
 struct Spectrum {
-    int expr = 0, nmodes = 0, capacity = 0;
-    size_t row = 0;                            // doubles of one row: nsys * nmodes * 2
-    DevBuf modes, partial, ring;               // modes: int32 [nmodes] in a buffer of doubles
-    int on_device = 0;                         // rows in the ring (the next record writes this row)
-    std::vector<double> rows;                  // drained, not fetched yet
+    int expr = 0, nmodes = 0;
+    DevBuf modes, partial;                     // modes: int32 [nmodes] in a buffer of doubles
+    RowRing ring;                              // a row: nsys * nmodes * 2 doubles
 };
 }  // namespace
 
 struct tf_spectrum : tf_observer {
     int nblk = 0, nseg = 0;
     std::vector<std::unique_ptr<Spectrum>> specs;
-
-    // the ring's rows to sp.rows, one copy (waits for the stream); the next record writes row 0
-    void drain(Spectrum& sp) {
-        if (sp.on_device == 0) return;
-        const size_t n = (size_t)sp.on_device * sp.row;
-        const size_t at = sp.rows.size();
-        sp.rows.resize(at + n);
-        tfb::d2h(sp.rows.data() + at, sp.ring.p, n * sizeof(double), solver->stream);
-        sp.on_device = 0;
-    }
 };
 
 extern "C" {
@@ -46,30 +31,26 @@ int tf_spectrum_create(tf_solver* s, const void* code_object, size_t code_size, 
     require(nspec >= 1 && nspec <= 64, "tf_spectrum_create: 1 ... 64 spectra");
     require(nconst >= 0, "tf_spectrum_create: bad constant count");
     std::unique_ptr<tf_spectrum> p(new tf_spectrum());
-    // The expressions of the block are numbered in the order the spectra first use them
-    // (SpectrumSet.expressions): a spectrum names one that an earlier spectrum named, or the next one.
-    // So no index passes that is not a case of tf_eval_spectrum in a block lowered from the same set.
     int nexpr = 0;
     for (int k = 0; k < nspec; ++k) {
         const int32_t* g = geometry + 3 * k;
         p->specs.emplace_back(new Spectrum());
         Spectrum& sp = *p->specs[k];
-        sp.expr = g[0]; sp.nmodes = g[1]; sp.capacity = g[2];
-        require(sp.expr >= 0 && sp.expr <= nexpr,
-                "tf_spectrum_create: expressions are numbered in the order the spectra first use them");
-        nexpr = std::max(nexpr, sp.expr + 1);
+        sp.expr = g[0]; sp.nmodes = g[1]; sp.ring.capacity = g[2];
+        tf_observer::require_numbered_in_order(
+            sp.expr, nexpr, "tf_spectrum_create: expressions are numbered in the order the spectra first use them");
         require(sp.nmodes >= 1 && sp.nmodes <= TF_SPEC_MAX_MODES, "tf_spectrum_create: 1 ... 64 modes per spectrum");
-        require(sp.capacity >= 1, "tf_spectrum_create: a ring has one row at least");
+        require(sp.ring.capacity >= 1, "tf_spectrum_create: a ring has one row at least");
     }
     p->init(s, code_object, code_size, nconst);
     p->nblk = (int)tf_solver::cdiv(s->L1.P, 256);
     p->nseg = (int)tf_solver::cdiv(s->L1.M, TF_PROBE_SEG);
     for (auto& spp : p->specs) {
         Spectrum& sp = *spp;
-        sp.row = (size_t)s->nsys * sp.nmodes * 2;
+        sp.ring.row = (size_t)s->nsys * sp.nmodes * 2;
         sp.modes.alloc(((size_t)sp.nmodes + 1) / 2, p->bytes);          // (zero-filled: mode 0 until set_modes)
         sp.partial.alloc((size_t)s->nsys * sp.nmodes * p->nseg * p->nblk * 2, p->bytes);
-        sp.ring.alloc((size_t)sp.capacity * sp.row, p->bytes);
+        sp.ring.alloc(p->bytes);
     }
     *out = p.release();
     TF_API_END
@@ -110,7 +91,7 @@ int tf_spectrum_record(tf_spectrum* p, int32_t which, int32_t slot) {
     require(which >= 0 && which < (int)p->specs.size(), "tf_spectrum_record: no such spectrum");
     tf_solver* s = p->solver;
     Spectrum& sp = *p->specs[which];
-    if (sp.on_device == sp.capacity) p->drain(sp);
+    const int row = sp.ring.next_row(s->stream);
     TfSpectrumArgs a;
     std::memset(&a, 0, sizeof a);
     static_cast<TfNodeArgs&>(a) = p->node_args(slot);
@@ -118,14 +99,14 @@ int tf_spectrum_record(tf_spectrum* p, int32_t which, int32_t slot) {
     a.nmodes = sp.nmodes;
     a.nblk = p->nblk;
     a.nseg = p->nseg;
-    a.row = sp.on_device;
-    a.capacity = sp.capacity;
+    a.row = row;
+    a.capacity = sp.ring.capacity;
     a.modes = (const int*)sp.modes.p;
     a.partial = sp.partial.p;
-    a.ring = sp.ring.p;
+    a.ring = sp.ring.ring.p;
     p->launch(TFK_SPECTRUM_PARTIAL, (unsigned)(s->nsys * p->nblk), (unsigned)p->nseg, 256, &a, sizeof a);
     p->launch(TFK_SPECTRUM_FINAL, (unsigned)s->nsys, 1, 256, &a, sizeof a);
-    ++sp.on_device;
+    ++sp.ring.on_device;
     TF_API_END
 }
 
@@ -133,13 +114,7 @@ int tf_spectrum_fetch(tf_spectrum* p, int32_t which, double* out, int64_t max_ro
     TF_API_BEGIN
     require(p && rows && (out || max_rows == 0), "null argument");
     require(which >= 0 && which < (int)p->specs.size(), "tf_spectrum_fetch: no such spectrum");
-    Spectrum& sp = *p->specs[which];
-    p->drain(sp);
-    const int64_t have = (int64_t)(sp.rows.size() / sp.row);
-    const int64_t n = std::min<int64_t>(have, std::max<int64_t>(max_rows, 0));
-    if (n) std::memcpy(out, sp.rows.data(), (size_t)n * sp.row * sizeof(double));
-    sp.rows.erase(sp.rows.begin(), sp.rows.begin() + (size_t)n * sp.row);
-    *rows = n;
+    p->specs[which]->ring.fetch(p->solver->stream, out, max_rows, rows);
     TF_API_END
 }
 
@@ -147,8 +122,7 @@ int tf_spectrum_pending(tf_spectrum* p, int32_t which, int64_t* rows) {
     TF_API_BEGIN
     require(p && rows, "null argument");
     require(which >= 0 && which < (int)p->specs.size(), "tf_spectrum_pending: no such spectrum");
-    const Spectrum& sp = *p->specs[which];
-    *rows = sp.on_device + (int64_t)(sp.rows.size() / sp.row);
+    *rows = p->specs[which]->ring.pending();
     TF_API_END
 }
 

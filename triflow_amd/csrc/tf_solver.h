@@ -13,6 +13,7 @@
 //   tf_rt_stat.cpp         device statistics (tf_stat_*)  }
 //   tf_rt_spectrum.cpp     device spectra (tf_spectrum_*) }
 //   tf_rt_extrema.cpp      device extrema (tf_extrema_*)  }
+//   tf_rt_histogram.cpp    device histograms (tf_histogram_*) }
 #pragma once
 #include "../../include/triflow_hip.h"
 #include "tf_args.h"
@@ -600,10 +601,11 @@ struct tf_solver {
     void check_status(const int* have_flag = nullptr, const double* have_worst = nullptr);
 };
 
-// What the device observers (tf_probe, tf_record, tf_stat, tf_spectrum, tf_extrema) share.  An observer is one more code object of the solver's
+// What the device observers (tf_probe, tf_record, tf_stat, tf_spectrum, tf_extrema, tf_histogram) share.  An observer is one more code object of the solver's
 // model -- the model's translation unit plus a generated block of expressions -- of which only the
 // observer's own kernels are launched, on the solver's stream, on one of its state slots.  Here: the inputs
-// of the node core (TfNodeArgs; csrc/tf_node.h) and the launch.  Rings and copies are the observer's own.
+// of the node core (TfNodeArgs; csrc/tf_node.h) and the launch.  Rings and copies are the observer's own
+// (the spectra, the extrema and the histograms: RowRing, below).
 struct tf_observer {
     tf_solver* solver = nullptr;
     tfb::Module* module = nullptr;
@@ -636,6 +638,14 @@ struct tf_observer {
     void set_x(const double* x) {
         if (own_x) solver->upload_planes(x, xplane.p, 1);
     }
+    // The expressions of a block are numbered in the order the items of the set first use them (the set's
+    // expressions() in Python): an item names one that an earlier item named, or the next one.  So no
+    // index passes that is not a case of the block's tf_eval_* when the block was lowered from the same
+    // set.  nexpr: the expressions named so far; msg: the caller's own words.
+    static void require_numbered_in_order(int expr, int& nexpr, const char* msg) {
+        require(expr >= 0 && expr <= nexpr, msg);
+        nexpr = std::max(nexpr, expr + 1);
+    }
     TfNodeArgs node_args(int slot) {
         tf_solver* s = solver;
         TfNodeArgs c;
@@ -661,4 +671,44 @@ struct tf_observer {
             tfb::launch(module, kernel, gx, gy, block, args, sz, s->stream);
         }
     }
+};
+
+// The ring of rows in device memory of an observer that writes one row per record (spectra, extrema,
+// histograms).  The host counts the rows and hands the row index to the kernels by value: nothing of the
+// ring's state lives on the device, and a record never waits.  The host waits only when the ring is full
+// (one copy of all of it before the next record) and when the caller fetches.  A record is
+//     row = next_row(stream);  build the arguments;  queue the launches;  ++on_device;
+// in this order: the drain comes before the arguments, the count after the last launch.
+struct RowRing {
+    int capacity = 0;                          // rows of the ring
+    size_t row = 0;                            // doubles of one row
+    DevBuf ring;
+    int on_device = 0;                         // rows in the ring (the next record writes this row)
+    std::vector<double> rows;                  // drained, not fetched yet
+
+    void alloc(int64_t& total) { ring.alloc((size_t)capacity * row, total); }
+    // the ring's rows to `rows`, one copy (waits for the stream); the next record writes row 0
+    void drain(tfb::Stream* stream) {
+        if (on_device == 0) return;
+        const size_t n = (size_t)on_device * row;
+        const size_t at = rows.size();
+        rows.resize(at + n);
+        tfb::d2h(rows.data() + at, ring.p, n * sizeof(double), stream);
+        on_device = 0;
+    }
+    // the row the next record writes (a full ring is drained first)
+    int next_row(tfb::Stream* stream) {
+        if (on_device == capacity) drain(stream);
+        return on_device;
+    }
+    // the oldest rows, max_rows at most, to out; what was not copied stays for the next fetch
+    void fetch(tfb::Stream* stream, double* out, int64_t max_rows, int64_t* nrows) {
+        drain(stream);
+        const int64_t have = (int64_t)(rows.size() / row);
+        const int64_t n = std::min<int64_t>(have, std::max<int64_t>(max_rows, 0));
+        if (n) std::memcpy(out, rows.data(), (size_t)n * row * sizeof(double));
+        rows.erase(rows.begin(), rows.begin() + (size_t)n * row);
+        *nrows = n;
+    }
+    int64_t pending() const { return on_device + (int64_t)(rows.size() / row); }
 };

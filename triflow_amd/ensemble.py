@@ -105,9 +105,7 @@ class Ensemble(Observed):
         self._x = x
         self._member_pars = [[np.asarray(v)[e] if np.ndim(v) >= 1 and np.shape(v)[0] == self.nsys else v
                               for v in values] for e in range(self.nsys)]
-        self._probes, self._recorders, self._statistics, self._spectra, self._nsteps = None, None, None, None, 0
-        self._extrema = None
-        self._histograms = None
+        self._nsteps = 0
 
     def step(self, dt):
         """One fixed step of every member (asynchronous: returns after the launches)."""
@@ -127,18 +125,8 @@ class Ensemble(Observed):
         self.cur = dst
         self.t += dt
         self._nsteps += 1
-        if self._probes is not None:
-            self._record_on(self._probes)
-        if self._recorders is not None:
-            self._record_on(self._recorders)
-        if self._statistics is not None:
-            self._record_on(self._statistics)
-        if self._spectra is not None:
-            self._record_on(self._spectra)
-        if self._extrema is not None:
-            self._record_on(self._extrema)
-        if self._histograms is not None:
-            self._record_on(self._histograms)
+        for series_set in self._observer_sets():
+            self._record_on(series_set)
 
     # ---- device probes and recorders (observers.Observed) ---------------------------------
     _n_nodes = property(lambda self: self.N)
@@ -166,18 +154,8 @@ class Ensemble(Observed):
     check = sync
 
     def close(self):
-        if self._probes is not None:
-            self._probes.close()
-        if self._recorders is not None:
-            self._recorders.close()
-        if self._statistics is not None:
-            self._statistics.close()
-        if self._spectra is not None:
-            self._spectra.close()
-        if self._extrema is not None:
-            self._extrema.close()
-        if self._histograms is not None:
-            self._histograms.close()
+        for series_set in self._observer_sets():
+            series_set.close()
         self.solver.close()
 
     def state(self):

@@ -27,7 +27,8 @@ launch arguments: sets that differ only in them share a code object.
 import numpy as np
 
 from . import codegen
-from .observers import ObserverSet, _Bound, discretise  # noqa: F401  (_Bound: the tests build one)
+from .observers import RowItem, RowObserverSet, _is_int, checked_capacity, checked_every, discretise
+from .observers import _Bound  # noqa: F401  (the tests build one)
 
 __all__ = ["ExtremaSet", "EXTREMA_KINDS", "MAX_COUNT", "DEFAULT_MAX_COUNT", "MAX_EXTREMA", "refine_parabola"]
 
@@ -47,17 +48,12 @@ def refine_parabola(xg, dx, vl, vc, vr):
     return xg + d * dx, vc - 0.25 * (vl - vr) * d
 
 
-class _Extrema:
+class _Extrema(RowItem):
     def __init__(self, name, expression, disc, kind, threshold, every, max_count, capacity, refine):
-        self.name, self.expression, self.disc = name, expression, disc
-        self.kind, self.threshold, self.every = kind, threshold, every
+        super().__init__(name, expression, disc, every)    # (a row: [nsys][1 + 4 * max_count])
+        self.kind, self.threshold = kind, threshold
         self.max_count, self.capacity, self.refine = max_count, capacity, refine
-        self.origin = None           # key of the state of the first row
-        self.last = None             # key of the state of the last row
-        self.pending = []            # rows on the device, in record order: (_Bound, t)
-        self.t, self.blocks = [], []   # fetched: t per row, arrays [rows][nsys][1 + 4 * max_count] in record order
         self.x = None                # [nsys][N]: the nodes' coordinates at the first row
-        self.nsys = 1
 
     def device_threshold(self):
         if self.threshold is not None:
@@ -65,7 +61,7 @@ class _Extrema:
         return -np.inf if self.kind == "max" else np.inf
 
 
-class ExtremaSet(ObserverSet):
+class ExtremaSet(RowObserverSet):
     """The extrema observers of one Simulation or Ensemble (``N`` nodes per system) and their series.
 
     Rows are recorded on the device (``record``) and fetched when the series are read (``series``):
@@ -73,28 +69,12 @@ class ExtremaSet(ObserverSet):
     sweep segment of those solvers."""
 
     kind = "extrema"
-
-    def __init__(self, model, N):
-        super().__init__(model)
-        self.N = int(N)
-        self._obs = []
+    _laid_out = "the extrema were laid out for"
 
     # ---- the set ---------------------------------------------------------------------
-    @property
-    def names(self):
-        return [r.name for r in self._obs]
-
-    def _get(self, name):
-        for r in self._obs:
-            if r.name == name:
-                return r
-        raise KeyError(name)
-
     def add(self, name, expression, kind="max", threshold=None, every=1, max_count=DEFAULT_MAX_COUNT,
             capacity=None, refine=True):
         """Validate, lower and append one observer (nothing is computed yet)."""
-        def integer(v):
-            return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer))
         if name in self.names:
             raise ValueError("an extrema observer named %r exists already" % (name,))
         if kind not in EXTREMA_KINDS:
@@ -104,99 +84,38 @@ class ExtremaSet(ObserverSet):
                     or not np.isfinite(threshold):
                 raise ValueError("extrema %r: threshold=%r, a finite number or None is expected" % (name, threshold))
             threshold = float(threshold)
-        if not integer(every) or every < 1:
-            raise ValueError("extrema %r: every=%r, an integer >= 1 is expected" % (name, every))
-        if not integer(max_count) or not 1 <= max_count <= MAX_COUNT:
+        every = checked_every("extrema", name, every)
+        if not _is_int(max_count) or not 1 <= max_count <= MAX_COUNT:
             raise ValueError("extrema %r: max_count=%r, an integer in 1 ... %d is expected" % (name, max_count, MAX_COUNT))
-        if capacity is not None and (not integer(capacity) or capacity < 1):
-            raise ValueError("extrema %r: capacity=%r, the ring has one row at least" % (name, capacity))
+        capacity = checked_capacity("extrema", name, capacity)
         if self.N < 3:
             raise ValueError("extrema %r: a grid of N=%d nodes, an extremum has two neighbours (N >= 3)" % (name, self.N))
-        if len(self._obs) >= MAX_EXTREMA:
+        if len(self._items) >= MAX_EXTREMA:
             raise ValueError("at most %d extrema observers per simulation (extrema %r)" % (MAX_EXTREMA, name))
         disc = discretise(self.model, expression)
         codegen.lower_extrema(self.model, [disc])          # (what the C emitter refuses, refused now)
         self._flush()
-        self._obs.append(_Extrema(name, expression, disc, kind, threshold, int(every), int(max_count),
-                                  None if capacity is None else int(capacity), bool(refine)))
-        self._reset()
-
-    def remove(self, name):
-        self._get(name)
-        self._flush()
-        self._obs = [r for r in self._obs if r.name != name]
+        self._items.append(_Extrema(name, expression, disc, kind, threshold, every, int(max_count), capacity,
+                                    bool(refine)))
         self._reset()
 
     # ---- device side -----------------------------------------------------------------
-    def expressions(self):
-        """The distinct discretised expressions of the set, in the order they were added: observers of
-        one expression share a case of the extrema block."""
-        out = []
-        for r in self._obs:
-            if r.disc not in out:
-                out.append(r.disc)
-        return out
-
     def _lower(self, mask):
         return codegen.lower_extrema(self.model, self.expressions(), parvec_mask=mask)
-
-    def _bind(self, solver):
-        if solver.N != self.N:
-            raise ValueError("the extrema were laid out for %d nodes, the solver has %d" % (self.N, solver.N))
-        return super()._bind(solver)
 
     def _make_handle(self, solver, code, spec):
         from ._capi import DeviceExtrema
         exprs = self.expressions()
         geometry = [(exprs.index(r.disc), EXTREMA_KINDS.index(r.kind), r.max_count, r.capacity or 0)
-                    for r in self._obs]
-        return DeviceExtrema(solver, code, geometry, [r.device_threshold() for r in self._obs],
+                    for r in self._items]
+        return DeviceExtrema(solver, code, geometry, [r.device_threshold() for r in self._items],
                              len(spec["host_consts"]))
 
-    def due(self, key):
-        """Indices of the observers that get a row for the state ``key`` (``key`` counts the steps): an
-        observer is due at its first state and every ``every`` keys after it, once per key."""
-        return [k for k, r in enumerate(self._obs)
-                if r.last != key and (r.origin is None or (key - r.origin) % r.every == 0)]
+    def _first_row(self, r, x, solver):
+        r.x = np.array(np.broadcast_to(x, (solver.nsys, self.N)))
 
-    def record(self, solver, slot, t, key, x, member_pars):
-        """Queue a row of every observer that is due (``due``): state ``slot`` of ``solver`` (a
-        ``DeviceSolver``).  ``x``: ``[N]`` or ``[nsys][N]``; ``member_pars``: per system, the model's
-        parameter values (the host constants of the expressions are computed from them).  An observer
-        that is not due costs nothing on the device."""
-        due = self.due(key)
-        if not due:
-            return
-        x = np.asarray(x, dtype=float)
-        b = self._bind_inputs(solver, x, member_pars)
-        for k in due:
-            r = self._obs[k]
-            b.handle.record(k, slot)
-            r.pending.append((b, t))
-            if r.origin is None:
-                r.origin = key
-                r.x = np.array(np.broadcast_to(x, (solver.nsys, self.N)))
-            r.last, r.nsys = key, solver.nsys
-
-    def _flush(self):
-        """Fetch every row still on the device and append it to the series."""
-        for k, r in enumerate(self._obs):
-            if not r.pending:
-                continue
-            bounds = []
-            for b, _ in r.pending:
-                if not any(b is o for o in bounds):
-                    bounds.append(b)
-            fetched = {id(b): b.handle.fetch(k) for b in bounds}
-            if len(bounds) == 1:
-                r.blocks.append(fetched[id(bounds[0])])
-            else:                                        # (several solvers in turn: row by row, in record order)
-                at = {id(b): 0 for b in bounds}
-                for b, _ in r.pending:
-                    r.blocks.append(fetched[id(b)][at[id(b)]:at[id(b)] + 1])
-                    at[id(b)] += 1
-            r.t.extend(t for _, t in r.pending)
-            r.pending.clear()
+    def _no_rows(self, r):
+        return np.zeros((0, r.nsys, 1 + 4 * r.max_count))
 
     @staticmethod
     def rows_of(raw, x, refine):
@@ -225,11 +144,9 @@ class ExtremaSet(ObserverSet):
         [rows], g, x, v [rows, max_count])."""
         self._flush()
         out = {}
-        for r in self._obs:
-            if len(r.blocks) != 1:
-                r.blocks = [np.concatenate(r.blocks) if r.blocks else np.zeros((0, r.nsys, 1 + 4 * r.max_count))]
+        for r in self._items:
             x = np.zeros((r.nsys, self.N)) if r.x is None else r.x
-            n, g, xx, v = self.rows_of(r.blocks[0], x, r.refine)
+            n, g, xx, v = self.rows_of(self._rows(r), x, r.refine)
             t = np.array(r.t, dtype=float)
             out[r.name] = (t, n, g, xx, v) if per_system else (t, n[:, 0], g[:, 0], xx[:, 0], v[:, 0])
         return out

@@ -29,7 +29,8 @@ same expressions share a code object whatever their edges, windows and strides.
 import numpy as np
 
 from . import codegen
-from .observers import ObserverSet, _Bound, discretise  # noqa: F401  (_Bound: the tests build one)
+from .observers import RowItem, RowObserverSet, _is_int, checked_capacity, checked_every, checked_nodes, discretise
+from .observers import _Bound  # noqa: F401  (the tests build one)
 
 __all__ = ["HistogramSet", "MAX_BINS", "DEFAULT_CAPACITY", "MAX_HISTOGRAMS", "bin_edges"]
 
@@ -40,10 +41,6 @@ MAX_BINS = 256
 DEFAULT_CAPACITY = 1024
 #: histograms of one set (tf_histogram_create)
 MAX_HISTOGRAMS = 64
-
-
-def _is_int(v):
-    return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer))
 
 
 def bin_edges(name, bins, range=None):
@@ -96,22 +93,17 @@ def bin_edges(name, bins, range=None):
     return edges
 
 
-class _Histogram:
+class _Histogram(RowItem):
     def __init__(self, name, expression, disc, edges, every, window, capacity):
-        self.name, self.expression, self.disc = name, expression, disc
-        self.edges, self.every, self.window, self.capacity = edges, every, window, capacity
-        self.origin = None           # key of the state of the first row
-        self.last = None             # key of the state of the last row
-        self.pending = []            # rows on the device, in record order: (_Bound, t)
-        self.t, self.blocks = [], []   # fetched: t per row, arrays [rows][nsys][nbins + 3] in record order
-        self.nsys = 1
+        super().__init__(name, expression, disc, every)    # (a row: [nsys][nbins + 3], int64)
+        self.edges, self.window, self.capacity = edges, window, capacity
 
     @property
     def nbins(self):
         return self.edges.size - 1
 
 
-class HistogramSet(ObserverSet):
+class HistogramSet(RowObserverSet):
     """The histograms of one Simulation or Ensemble (``N`` nodes per system) and their series.
 
     Rows are recorded on the device (``record``) and fetched when the series are read (``series``):
@@ -119,137 +111,46 @@ class HistogramSet(ObserverSet):
     sweep segment of those solvers."""
 
     kind = "histogram"
-
-    def __init__(self, model, N):
-        super().__init__(model)
-        self.N = int(N)
-        self._hists = []
+    _laid_out = "the histogram windows were laid out for"
 
     # ---- the set ---------------------------------------------------------------------
-    @property
-    def names(self):
-        return [r.name for r in self._hists]
-
-    def _get(self, name):
-        for r in self._hists:
-            if r.name == name:
-                return r
-        raise KeyError(name)
-
     def add(self, name, expression, bins, range=None, every=1, nodes=slice(None), capacity=None):
         """Validate, lower and append one histogram (nothing is computed yet)."""
         if name in self.names:
             raise ValueError("a histogram named %r exists already" % (name,))
-        if not _is_int(every) or every < 1:
-            raise ValueError("histogram %r: every=%r, an integer >= 1 is expected" % (name, every))
+        every = checked_every("histogram", name, every)
         edges = bin_edges(name, bins, range)
-        if not isinstance(nodes, slice):
-            raise ValueError("histogram %r: nodes=%r, a slice is expected" % (name, nodes))
-        try:
-            window = nodes.indices(self.N)
-        except (TypeError, ValueError) as exc:
-            raise ValueError("histogram %r: nodes=%r: %s" % (name, nodes, exc))
-        if window[2] < 1:
-            raise ValueError("histogram %r: nodes=%r, a step >= 1 is expected" % (name, nodes))
-        if window[1] <= window[0]:
-            raise ValueError("histogram %r: nodes=%r holds no node of a grid of %d" % (name, nodes, self.N))
-        if capacity is not None and (not _is_int(capacity) or capacity < 1):
-            raise ValueError("histogram %r: capacity=%r, the ring has one row at least" % (name, capacity))
-        if len(self._hists) >= MAX_HISTOGRAMS:
+        window = checked_nodes("histogram", name, nodes, self.N)
+        capacity = checked_capacity("histogram", name, capacity)
+        if len(self._items) >= MAX_HISTOGRAMS:
             raise ValueError("at most %d histograms per simulation (histogram %r)" % (MAX_HISTOGRAMS, name))
         disc = discretise(self.model, expression)
         codegen.lower_histograms(self.model, [disc])       # (what the C emitter refuses, refused now)
         self._flush()
-        self._hists.append(_Histogram(name, expression, disc, edges, int(every), window,
-                                      DEFAULT_CAPACITY if capacity is None else int(capacity)))
-        self._reset()
-
-    def remove(self, name):
-        self._get(name)
-        self._flush()
-        self._hists = [r for r in self._hists if r.name != name]
+        self._items.append(_Histogram(name, expression, disc, edges, every, window,
+                                      DEFAULT_CAPACITY if capacity is None else capacity))
         self._reset()
 
     # ---- device side -----------------------------------------------------------------
-    def expressions(self):
-        """The distinct discretised expressions of the set, in the order they were added: histograms of
-        one expression share a case of the histogram block (and sets that differ only in edges, windows
-        or strides share a code object)."""
-        out = []
-        for r in self._hists:
-            if r.disc not in out:
-                out.append(r.disc)
-        return out
-
     def _lower(self, mask):
         return codegen.lower_histograms(self.model, self.expressions(), parvec_mask=mask)
-
-    def _bind(self, solver):
-        if solver.N != self.N:
-            raise ValueError("the histogram windows were laid out for %d nodes, the solver has %d"
-                             % (self.N, solver.N))
-        return super()._bind(solver)
 
     def _make_handle(self, solver, code, spec):
         from ._capi import DeviceHistogram
         exprs = self.expressions()
-        geometry = [(exprs.index(r.disc), r.nbins, r.capacity, *r.window) for r in self._hists]
-        return DeviceHistogram(solver, code, geometry, [r.edges for r in self._hists], len(spec["host_consts"]))
+        geometry = [(exprs.index(r.disc), r.nbins, r.capacity, *r.window) for r in self._items]
+        return DeviceHistogram(solver, code, geometry, [r.edges for r in self._items], len(spec["host_consts"]))
 
-    def due(self, key):
-        """Indices of the histograms that get a row for the state ``key`` (``key`` counts the steps): a
-        histogram is due at its first state and every ``every`` keys after it, once per key."""
-        return [k for k, r in enumerate(self._hists)
-                if r.last != key and (r.origin is None or (key - r.origin) % r.every == 0)]
-
-    def record(self, solver, slot, t, key, x, member_pars):
-        """Queue a row of every histogram that is due (``due``): state ``slot`` of ``solver`` (a
-        ``DeviceSolver``).  ``x``: ``[N]`` or ``[nsys][N]``; ``member_pars``: per system, the model's
-        parameter values (the host constants of the expressions are computed from them).  A histogram
-        that is not due costs nothing on the device."""
-        due = self.due(key)
-        if not due:
-            return
-        x = np.asarray(x, dtype=float)
-        b = self._bind_inputs(solver, x, member_pars)
-        for k in due:
-            r = self._hists[k]
-            b.handle.record(k, slot)
-            r.pending.append((b, t))
-            if r.origin is None:
-                r.origin = key
-            r.last, r.nsys = key, solver.nsys
-
-    def _flush(self):
-        """Fetch every row still on the device and append it to the series."""
-        for k, r in enumerate(self._hists):
-            if not r.pending:
-                continue
-            bounds = []
-            for b, _ in r.pending:
-                if not any(b is o for o in bounds):
-                    bounds.append(b)
-            fetched = {id(b): b.handle.fetch(k) for b in bounds}
-            if len(bounds) == 1:
-                r.blocks.append(fetched[id(bounds[0])])
-            else:                                        # (several solvers in turn: row by row, in record order)
-                at = {id(b): 0 for b in bounds}
-                for b, _ in r.pending:
-                    r.blocks.append(fetched[id(b)][at[id(b)]:at[id(b)] + 1])
-                    at[id(b)] += 1
-            r.t.extend(t for _, t in r.pending)
-            r.pending.clear()
+    def _no_rows(self, r):
+        return np.zeros((0, r.nsys, r.nbins + 3), dtype=np.int64)
 
     def series(self, per_system=True):
         """name -> (t [rows], edges [nbins + 1], counts [rows, nsys, nbins], outside [rows, nsys, 3]), int64
         counts (``per_system=False``: counts [rows, nbins], outside [rows, 3])."""
         self._flush()
         out = {}
-        for r in self._hists:
-            if len(r.blocks) != 1:
-                r.blocks = [np.concatenate(r.blocks) if r.blocks
-                            else np.zeros((0, r.nsys, r.nbins + 3), dtype=np.int64)]
-            c = r.blocks[0] if per_system else r.blocks[0][:, 0]
+        for r in self._items:
+            c = self._rows(r) if per_system else self._rows(r)[:, 0]
             out[r.name] = (np.array(r.t, dtype=float), r.edges.copy(),
                            np.ascontiguousarray(c[..., :r.nbins]), np.ascontiguousarray(c[..., r.nbins:]))
         return out

@@ -3,14 +3,22 @@
 (``histograms.py``) share.
 
 An observer evaluates expressions in the model's own string language at the nodes of a resident state
-slot and writes one row per record into a ring in device memory.  Both kinds go through the same node
-core (``csrc/tf_node.h``): the expressions are discretised with the model's stencils (``discretise``),
-lowered to a block of C that follows the model's translation unit, and compiled into one more code
-object of the model (``compilers.build_observer_code_object``); a handle per solver binds it
-(``_capi.DeviceProbe`` / ``DeviceRecord``) and is fed ``x`` and the host constants of the expressions.
-:class:`ObserverSet` owns that part.  A kind of observer supplies the lowering of its expressions, its
-handle, and what a row is.
+slot.  All kinds go through the same node core (``csrc/tf_node.h``): the expressions are discretised with
+the model's stencils (``discretise``), lowered to a block of C that follows the model's translation unit,
+and compiled into one more code object of the model (``compilers.build_observer_code_object``); a handle
+per solver binds it (``_capi.DeviceProbe`` ...) and is fed ``x`` and the host constants of the
+expressions.  :class:`ObserverSet` owns that part.
+
+:class:`ItemObserverSet` adds what the sets of named items with a stride share (all kinds but the probes):
+the item list, the distinct expressions, the due rule, the check of the solver's grid, and the validators
+of ``every``, ``nodes`` and ``capacity`` (``checked_*``).  :class:`RowObserverSet` adds the series of the
+kinds that write one row per record into a ring per item (recorders, spectra, extrema, histograms):
+``record``, the fetch of the rows still on the device (``_flush``) and their joining.  A kind supplies its
+item, the specific parts of ``add``, the lowering of its expressions, its handle and what a row is.
+:class:`Observed` is the ``add_*`` / ``remove_*`` side of the front ends.
 """
+
+import importlib
 
 import numpy as np
 import sympy as sp
@@ -19,7 +27,7 @@ from sympy.core.function import AppliedUndef
 from . import codegen
 from .codegen import UnsupportedExpression
 
-__all__ = ["ObserverSet", "Observed", "discretise"]
+__all__ = ["ObserverSet", "ItemObserverSet", "RowObserverSet", "Observed", "discretise"]
 
 
 def discretise(model, expression):
@@ -64,8 +72,9 @@ class _Bound:
 class ObserverSet:
     """The code objects and handles of a set of observers: one handle per solver the set has run on, one
     code object per parameter layout / sweep segment of those solvers.  Subclasses: ``kind`` ("probe" /
-    "record" / "stat" / "spectrum" / "extrema" / "histogram": ``compilers.build_observer_code_object``), ``_lower(mask) -> (block, spec)``,
-    ``_make_handle(solver, code, spec)`` and ``_flush()`` (every row still on the device to the series)."""
+    "record" / "stat" / "spectrum" / "extrema" / "histogram": ``compilers.build_observer_code_object``),
+    ``_lower(mask) -> (block, spec)``, ``_make_handle(solver, code, spec)`` and ``_flush()`` (everything
+    still on the device to the host)."""
 
     kind = None
 
@@ -122,19 +131,196 @@ class ObserverSet:
         return b
 
 
+def _is_int(v):
+    """An integer, and not a bool (Python's or NumPy's)."""
+    return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer))
+
+
+def checked_every(noun, name, every):
+    """``every`` of ``add`` as an int, or ``ValueError`` (``noun``: "recorder", "spectrum" ...)."""
+    if not _is_int(every) or every < 1:
+        raise ValueError("%s %r: every=%r, an integer >= 1 is expected" % (noun, name, every))
+    return int(every)
+
+
+def checked_nodes(noun, name, nodes, N):
+    """``nodes`` of ``add`` as ``slice.indices(N)`` with a step >= 1 and a node at least, or ``ValueError``."""
+    if not isinstance(nodes, slice):
+        raise ValueError("%s %r: nodes=%r, a slice is expected" % (noun, name, nodes))
+    try:
+        window = nodes.indices(N)
+    except (TypeError, ValueError) as exc:
+        raise ValueError("%s %r: nodes=%r: %s" % (noun, name, nodes, exc))
+    if window[2] < 1:
+        raise ValueError("%s %r: nodes=%r, a step >= 1 is expected" % (noun, name, nodes))
+    if window[1] <= window[0]:
+        raise ValueError("%s %r: nodes=%r holds no node of a grid of %d" % (noun, name, nodes, N))
+    return window
+
+
+def checked_capacity(noun, name, capacity):
+    """``capacity`` of ``add`` (rows of a ring of one row at least) as an int, None as None, or ``ValueError``."""
+    if capacity is None:
+        return None
+    if not _is_int(capacity) or capacity < 1:
+        raise ValueError("%s %r: capacity=%r, the ring has one row at least" % (noun, name, capacity))
+    return int(capacity)
+
+
+class ItemObserverSet(ObserverSet):
+    """A set of named items -- each an expression and a stride ``every`` -- laid out for a grid of ``N``
+    nodes: what the statistics share with the kinds that record rows.  An item has ``name``, ``disc``,
+    ``every``, ``origin`` and ``last`` (the keys of its first and its latest state).  Subclasses:
+    ``_laid_out``, the opening of the message for a solver of another grid."""
+
+    _laid_out = None
+
+    def __init__(self, model, N):
+        super().__init__(model)
+        self.N = int(N)
+        self._items = []
+
+    @property
+    def names(self):
+        return [r.name for r in self._items]
+
+    def _get(self, name):
+        for r in self._items:
+            if r.name == name:
+                return r
+        raise KeyError(name)
+
+    def remove(self, name):
+        self._get(name)
+        self._flush()
+        self._items = [r for r in self._items if r.name != name]
+        self._reset()
+
+    def expressions(self):
+        """The distinct discretised expressions of the set, in the order they were added: items of one
+        expression share a case of the generated block, and sets that differ only in what is data of
+        the handle or a launch argument share a code object."""
+        out = []
+        for r in self._items:
+            if r.disc not in out:
+                out.append(r.disc)
+        return out
+
+    def _bind(self, solver):
+        if solver.N != self.N:
+            raise ValueError("%s %d nodes, the solver has %d" % (self._laid_out, self.N, solver.N))
+        return super()._bind(solver)
+
+    def due(self, key):
+        """Indices of the items that take the state ``key`` (``key`` counts the steps): an item is due
+        at its first state and every ``every`` keys after it, once per key."""
+        return [k for k, r in enumerate(self._items)
+                if r.last != key and (r.origin is None or (key - r.origin) % r.every == 0)]
+
+
+class RowItem:
+    """What an item of a :class:`RowObserverSet` keeps of its series."""
+
+    def __init__(self, name, expression, disc, every):
+        self.name, self.expression, self.disc, self.every = name, expression, disc, every
+        self.origin = None           # key of the state of the first row
+        self.last = None             # key of the state of the last row
+        self.pending = []            # rows on the device, in record order: (_Bound, t)
+        self.t, self.blocks = [], []   # fetched: t per row, arrays [rows][nsys][width] in record order
+        self.nsys = 1
+
+
+class RowObserverSet(ItemObserverSet):
+    """The kinds that write one row per record into a ring of their item on the device (recorders,
+    spectra, extrema, histograms): rows are queued by ``record`` and come to the host, whole rings at a
+    time, when the series are read, the set changes or it is closed (``_flush``).  The handle has
+    ``record(k, slot)`` and ``fetch(k) -> [rows][nsys][width]``.  Subclasses: ``_first_row`` where an
+    item keeps something of the grid, and ``_no_rows``."""
+
+    def record(self, solver, slot, t, key, x, member_pars):
+        """Queue a row of every item that is due (``due``): state ``slot`` of ``solver`` (a
+        ``DeviceSolver``).  ``x``: ``[N]`` or ``[nsys][N]``; ``member_pars``: per system, the model's
+        parameter values (the host constants of the expressions are computed from them).  An item
+        that is not due costs nothing on the device."""
+        due = self.due(key)
+        if not due:
+            return
+        x = np.asarray(x, dtype=float)
+        b = self._bind_inputs(solver, x, member_pars)
+        for k in due:
+            r = self._items[k]
+            b.handle.record(k, slot)
+            r.pending.append((b, t))
+            if r.origin is None:
+                r.origin = key
+                self._first_row(r, x, solver)
+            r.last, r.nsys = key, solver.nsys
+
+    def _first_row(self, item, x, solver):
+        """What ``item`` keeps of the grid ``x`` (``[N]`` or ``[nsys][N]``) of its first row."""
+
+    def _flush(self):
+        """Fetch every row still on the device and append it to the series (whole blocks: the rows of
+        a long run are copied once here and once when the blocks are joined)."""
+        for k, r in enumerate(self._items):
+            if not r.pending:
+                continue
+            bounds = []
+            for b, _ in r.pending:
+                if not any(b is o for o in bounds):
+                    bounds.append(b)
+            fetched = {id(b): b.handle.fetch(k) for b in bounds}
+            if len(bounds) == 1:
+                r.blocks.append(fetched[id(bounds[0])])
+            else:                                        # (several solvers in turn: row by row, in record order)
+                at = {id(b): 0 for b in bounds}
+                for b, _ in r.pending:
+                    r.blocks.append(fetched[id(b)][at[id(b)]:at[id(b)] + 1])
+                    at[id(b)] += 1
+            r.t.extend(t for _, t in r.pending)
+            r.pending.clear()
+
+    def _rows(self, item):
+        """The fetched rows of ``item`` as one array ``[rows][nsys][width]`` (``_no_rows(item)`` when
+        there are none), kept as its only block."""
+        if len(item.blocks) != 1:
+            item.blocks = [np.concatenate(item.blocks) if item.blocks else self._no_rows(item)]
+        return item.blocks[0]
+
+
 class Observed:
     """``add_probe`` / ``add_recorder`` / ``add_statistic`` / ``add_spectrum`` / ``add_extrema`` /
     ``add_histogram`` ... of a front end (``Simulation``, ``Ensemble``): reductions over space, decimated
     space-time pictures, reductions over time, Fourier amplitudes, the crests and troughs and the
-    distribution of values over time.  The front end
-    has ``model``, says how a set records its current state (``_record_on(series_set)``: also called after
-    every step for ``_probes``, ``_recorders``, ``_statistics``, ``_spectra``, ``_extrema`` and ``_histograms`` that are not None), how many nodes a system has
-    (``_n_nodes``) and whether its series keep the axis of the systems (``_per_system``)."""
+    distribution of values over time.  The front end has ``model``, says how a set records its current
+    state (``_record_on(series_set)``: it also calls it after every step for each of ``_observer_sets()``),
+    how many nodes a system has (``_n_nodes``) and whether its series keep the axis of the systems
+    (``_per_system``)."""
 
+    #: the kinds, in the order they record a state: the attribute that holds the set (None until the first
+    #: ``add_*``), its module and class, and whether the set is laid out for the number of nodes
+    _KINDS = (("_probes", "probes", "ProbeSet", False),
+              ("_recorders", "recorders", "RecorderSet", True),
+              ("_statistics", "statistics", "StatisticSet", True),
+              ("_spectra", "spectra", "SpectrumSet", True),
+              ("_extrema", "extrema", "ExtremaSet", True),
+              ("_histograms", "histograms", "HistogramSet", True))
     _probes = _recorders = _statistics = _spectra = _extrema = _histograms = None
     _per_system = True
 
-    def _add_observer(self, series_set, name, *args):
+    def _observer_sets(self):
+        """The sets that exist, in the order of ``_KINDS``."""
+        return [getattr(self, attr) for attr, *_ in self._KINDS if getattr(self, attr) is not None]
+
+    def _add_observer(self, attr, name, *args):
+        """``add(name, *args)`` on the set ``attr``, created now if this is its first item, and a row of
+        the current state."""
+        series_set = getattr(self, attr)
+        if series_set is None:
+            _, module, cls, takes_n = next(kind for kind in self._KINDS if kind[0] == attr)
+            cls = getattr(importlib.import_module("." + module, __package__), cls)
+            series_set = cls(self.model, self._n_nodes) if takes_n else cls(self.model)
+            setattr(self, attr, series_set)
         series_set.add(name, *args)
         try:
             self._record_on(series_set)
@@ -143,6 +329,16 @@ class Observed:
             series_set.remove(name)
             raise
 
+    def _observer_set_of(self, attr, name):
+        """The set ``attr`` that should hold ``name``; ``KeyError(name)`` when nothing was ever added to it."""
+        if getattr(self, attr) is None:
+            raise KeyError(name)
+        return getattr(self, attr)
+
+    def _series(self, attr):
+        series_set = getattr(self, attr)
+        return series_set.series(per_system=self._per_system) if series_set is not None else {}
+
     # ---- device probes (probes.py) ----------------------------------------------------
     def add_probe(self, name, expression, reduce="sum"):
         """Record ``reduce`` of the model expression ``expression`` over the nodes (of every member of
@@ -150,20 +346,15 @@ class Observed:
         every step (a Simulation: where the post-processes run).  The series is ``probes[name] =
         (t, values)``, an Ensemble's ``(t, values[rows, nsys])`` of this rank's members only; the
         fields are never brought to the host for it."""
-        if self._probes is None:
-            from .probes import ProbeSet
-            self._probes = ProbeSet(self.model)
-        self._add_observer(self._probes, name, expression, reduce)
+        self._add_observer("_probes", name, expression, reduce)
 
     def remove_probe(self, name):
-        if self._probes is None:
-            raise KeyError(name)
-        self._probes.remove(name)
+        self._observer_set_of("_probes", name).remove(name)
 
     @property
     def probes(self):
         """name -> (t, values): float64 arrays, one entry per recorded state."""
-        return self._probes.series(per_system=self._per_system) if self._probes is not None else {}
+        return self._series("_probes")
 
     # ---- device recorders (recorders.py) ----------------------------------------------
     def add_recorder(self, name, expression, every=1, nodes=slice(None), pool="sample", capacity=None):
@@ -173,20 +364,15 @@ class Observed:
         The series is ``recorders[name] = (t, x, values[rows, ncols])``, an Ensemble's ``(t, x,
         values[rows, nsys, ncols])`` with ``x [nsys, ncols]`` when the members have grids of their own,
         of this rank's members only; the fields never come to the host for it."""
-        if self._recorders is None:
-            from .recorders import RecorderSet
-            self._recorders = RecorderSet(self.model, self._n_nodes)
-        self._add_observer(self._recorders, name, expression, every, nodes, pool, capacity)
+        self._add_observer("_recorders", name, expression, every, nodes, pool, capacity)
 
     def remove_recorder(self, name):
-        if self._recorders is None:
-            raise KeyError(name)
-        self._recorders.remove(name)
+        self._observer_set_of("_recorders", name).remove(name)
 
     @property
     def recorders(self):
         """name -> (t, x, values): float64 arrays, one row of values per recorded state."""
-        return self._recorders.series(per_system=self._per_system) if self._recorders is not None else {}
+        return self._series("_recorders")
 
     # ---- device statistics (statistics.py) --------------------------------------------
     def add_statistic(self, name, expression, stat="mean", every=1, nodes=slice(None)):
@@ -197,26 +383,19 @@ class Observed:
         ``statistics[name] = (n, x, values[ncols])`` at the nodes ``nodes`` (a slice), an Ensemble's
         ``(n, x, values[nsys, ncols])`` of this rank's members only; the fields never come to the host
         for it."""
-        if self._statistics is None:
-            from .statistics import StatisticSet
-            self._statistics = StatisticSet(self.model, self._n_nodes)
-        self._add_observer(self._statistics, name, expression, stat, every, nodes)
+        self._add_observer("_statistics", name, expression, stat, every, nodes)
 
     def remove_statistic(self, name):
-        if self._statistics is None:
-            raise KeyError(name)
-        self._statistics.remove(name)
+        self._observer_set_of("_statistics", name).remove(name)
 
     def reset_statistic(self, name):
         """Drop the samples taken so far (a transient): the next due state is sample 1 again."""
-        if self._statistics is None:
-            raise KeyError(name)
-        self._statistics.reset(name)
+        self._observer_set_of("_statistics", name).reset(name)
 
     @property
     def statistics(self):
         """name -> (n, x, values): the samples folded so far, float64 arrays over the nodes."""
-        return self._statistics.series(per_system=self._per_system) if self._statistics is not None else {}
+        return self._series("_statistics")
 
     # ---- device spectra (spectra.py) ----------------------------------------------------
     def add_spectrum(self, name, expression, modes, every=1, capacity=None):
@@ -230,20 +409,15 @@ class Observed:
         the wavenumbers ``k = 2 * pi * modes / (N * dx)`` and ``c`` complex128, an Ensemble's ``(t, k,
         c[rows, nsys, nmodes])`` with ``k [nsys, nmodes]`` when the members have grids of their own, of
         this rank's members only; the fields never come to the host for it."""
-        if self._spectra is None:
-            from .spectra import SpectrumSet
-            self._spectra = SpectrumSet(self.model, self._n_nodes)
-        self._add_observer(self._spectra, name, expression, modes, every, capacity)
+        self._add_observer("_spectra", name, expression, modes, every, capacity)
 
     def remove_spectrum(self, name):
-        if self._spectra is None:
-            raise KeyError(name)
-        self._spectra.remove(name)
+        self._observer_set_of("_spectra", name).remove(name)
 
     @property
     def spectra(self):
         """name -> (t, k, c): float64 times and wavenumbers, one complex128 row of c per recorded state."""
-        return self._spectra.series(per_system=self._per_system) if self._spectra is not None else {}
+        return self._series("_spectra")
 
     # ---- device extrema (extrema.py) ----------------------------------------------------
     def add_extrema(self, name, expression, kind="max", threshold=None, every=1, max_count=256, capacity=None,
@@ -262,21 +436,16 @@ class Observed:
         neighbours (``refine=True``) or the node's own ``x`` and ``v[g]`` (``refine=False``).  An
         Ensemble's: ``n[rows, nsys]`` and ``g, x, v [rows, nsys, max_count]``, of this rank's members only;
         the fields never come to the host for it."""
-        if self._extrema is None:
-            from .extrema import ExtremaSet
-            self._extrema = ExtremaSet(self.model, self._n_nodes)
-        self._add_observer(self._extrema, name, expression, kind, threshold, every, max_count, capacity, refine)
+        self._add_observer("_extrema", name, expression, kind, threshold, every, max_count, capacity, refine)
 
     def remove_extrema(self, name):
-        if self._extrema is None:
-            raise KeyError(name)
-        self._extrema.remove(name)
+        self._observer_set_of("_extrema", name).remove(name)
 
     @property
     def extrema(self):
         """name -> (t, n, g, x, v): float64 times, int64 counts and nodes, float64 positions and values,
         one row per recorded state."""
-        return self._extrema.series(per_system=self._per_system) if self._extrema is not None else {}
+        return self._series("_extrema")
 
     # ---- device histograms (histograms.py) ------------------------------------------------
     def add_histogram(self, name, expression, bins, range=None, every=1, nodes=slice(None), capacity=None):
@@ -293,18 +462,13 @@ class Observed:
         Ensemble's: ``counts[rows, nsys, nbins]`` and ``outside[rows, nsys, 3]``, one ``edges`` for all
         members, of this rank's members only; the fields never come to the host for it.  Nothing is
         accumulated over time on the device: that is ``counts.sum(0)``."""
-        if self._histograms is None:
-            from .histograms import HistogramSet
-            self._histograms = HistogramSet(self.model, self._n_nodes)
-        self._add_observer(self._histograms, name, expression, bins, range, every, nodes, capacity)
+        self._add_observer("_histograms", name, expression, bins, range, every, nodes, capacity)
 
     def remove_histogram(self, name):
-        if self._histograms is None:
-            raise KeyError(name)
-        self._histograms.remove(name)
+        self._observer_set_of("_histograms", name).remove(name)
 
     @property
     def histograms(self):
         """name -> (t, edges, counts, outside): float64 times and edges, int64 counts, one row per
         recorded state."""
-        return self._histograms.series(per_system=self._per_system) if self._histograms is not None else {}
+        return self._series("_histograms")

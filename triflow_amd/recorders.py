@@ -19,7 +19,8 @@ import numpy as np
 
 from . import codegen
 from .codegen import RECORD_POOLS
-from .observers import ObserverSet, _Bound, discretise  # noqa: F401  (_Bound: the tests build one)
+from .observers import RowItem, RowObserverSet, _is_int, checked_every, checked_nodes, discretise
+from .observers import _Bound  # noqa: F401  (the tests build one)
 
 __all__ = ["RecorderSet", "RECORD_POOLS", "DEFAULT_RING_BYTES", "MAX_RING_ROWS", "MAX_RECORDERS"]
 
@@ -31,18 +32,13 @@ MAX_RING_ROWS = 2048
 MAX_RECORDERS = 64
 
 
-class _Recorder:
+class _Recorder(RowItem):
     def __init__(self, name, expression, disc, every, window, pool, capacity):
-        self.name, self.expression, self.disc = name, expression, disc
-        self.every, self.pool, self.capacity = every, pool, capacity
+        super().__init__(name, expression, disc, every)    # (a row: [nsys][ncols])
+        self.pool, self.capacity = pool, capacity
         self.start, self.stop, self.step = window
         self.ncols = -(-(self.stop - self.start) // self.step)
-        self.origin = None           # key of the state of the first row
-        self.last = None             # key of the state of the last row
-        self.pending = []            # rows on the device, in record order: (_Bound, t)
-        self.t, self.blocks = [], []   # fetched: t per row, arrays [rows][nsys][ncols] in record order
         self.x = None                # [ncols] or [nsys][ncols]
-        self.nsys = 1
 
     def rows_of_ring(self, nsys):
         """Rows of the device ring (both halves) on a solver of ``nsys`` systems."""
@@ -56,7 +52,7 @@ class _Recorder:
         return max(2, min(DEFAULT_RING_BYTES // row, MAX_RING_ROWS) & ~1)
 
 
-class RecorderSet(ObserverSet):
+class RecorderSet(RowObserverSet):
     """The recorders of one Simulation or Ensemble (``N`` nodes per system) and their series.
 
     Rows are recorded on the device (``record``) and fetched when the series are read (``series``):
@@ -65,139 +61,58 @@ class RecorderSet(ObserverSet):
     ``DEFAULT_RING_BYTES`` worth of rows)."""
 
     kind = "record"
+    _laid_out = "the recorders were laid out for"
 
     def __init__(self, model, N, capacity=None):
-        super().__init__(model)
-        self.N = int(N)
+        super().__init__(model, N)
         self.capacity = capacity
-        self._recs = []
 
     # ---- the set ---------------------------------------------------------------------
-    @property
-    def names(self):
-        return [r.name for r in self._recs]
-
-    def _get(self, name):
-        for r in self._recs:
-            if r.name == name:
-                return r
-        raise KeyError(name)
-
     def add(self, name, expression, every=1, nodes=slice(None), pool="sample", capacity=None):
         """Validate, lower and append one recorder (nothing is computed yet)."""
         if pool not in RECORD_POOLS:
             raise ValueError("unknown recorder pool %r (one of %s)" % (pool, ", ".join(RECORD_POOLS)))
         if name in self.names:
             raise ValueError("a recorder named %r exists already" % (name,))
-        if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or every < 1:
-            raise ValueError("recorder %r: every=%r, an integer >= 1 is expected" % (name, every))
-        if not isinstance(nodes, slice):
-            raise ValueError("recorder %r: nodes=%r, a slice is expected" % (name, nodes))
-        try:
-            window = nodes.indices(self.N)
-        except (TypeError, ValueError) as exc:
-            raise ValueError("recorder %r: nodes=%r: %s" % (name, nodes, exc))
-        if window[2] < 1:
-            raise ValueError("recorder %r: nodes=%r, a step >= 1 is expected" % (name, nodes))
-        if window[1] <= window[0]:
-            raise ValueError("recorder %r: nodes=%r holds no node of a grid of %d" % (name, nodes, self.N))
+        every = checked_every("recorder", name, every)
+        window = checked_nodes("recorder", name, nodes, self.N)
         capacity = self.capacity if capacity is None else capacity
-        if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer))
-                                     or capacity < 2):
+        if capacity is not None and (not _is_int(capacity) or capacity < 2):
             raise ValueError("recorder %r: capacity=%r, the ring has two rows at least (one per half)"
                              % (name, capacity))
-        if len(self._recs) >= MAX_RECORDERS:
+        if len(self._items) >= MAX_RECORDERS:
             raise ValueError("at most %d recorders per simulation" % MAX_RECORDERS)
         disc = discretise(self.model, expression)
         codegen.lower_records(self.model, [disc])          # (what the C emitter refuses, refused now)
         self._flush()
-        self._recs.append(_Recorder(name, expression, disc, int(every), window, pool,
-                                    None if capacity is None else int(capacity) & ~1))
-        self._reset()
-
-    def remove(self, name):
-        self._get(name)
-        self._flush()
-        self._recs = [r for r in self._recs if r.name != name]
+        self._items.append(_Recorder(name, expression, disc, every, window, pool,
+                                     None if capacity is None else int(capacity) & ~1))
         self._reset()
 
     # ---- device side -----------------------------------------------------------------
-    def expressions(self):
-        """The distinct discretised expressions of the set, in the order they were added: recorders
-        of one expression share a case of the record block (and sets that differ only in geometry
-        share a code object)."""
-        out = []
-        for r in self._recs:
-            if r.disc not in out:
-                out.append(r.disc)
-        return out
-
     def _lower(self, mask):
         return codegen.lower_records(self.model, self.expressions(), parvec_mask=mask)
-
-    def _bind(self, solver):
-        if solver.N != self.N:
-            raise ValueError("the recorders were laid out for %d nodes, the solver has %d" % (self.N, solver.N))
-        return super()._bind(solver)
 
     def _make_handle(self, solver, code, spec):
         from ._capi import DeviceRecord
         exprs = self.expressions()
         geometry = [(exprs.index(r.disc), RECORD_POOLS.index(r.pool), r.start, r.stop, r.step, r.rows_of_ring(solver.nsys))
-                    for r in self._recs]
+                    for r in self._items]
         return DeviceRecord(solver, code, geometry, len(spec["host_consts"]))
 
-    def record(self, solver, slot, t, key, x, member_pars):
-        """Queue a row of every recorder that is due: state ``slot`` of ``solver`` (a ``DeviceSolver``).
-        ``key`` counts the steps (a recorder is due at its first state and every ``every`` keys after
-        it, once per key); ``x``: ``[N]`` or ``[nsys][N]``; ``member_pars``: per system, the model's
-        parameter values (the host constants of the expressions are computed from them).  A recorder
-        that is not due costs nothing on the device."""
-        due = [k for k, r in enumerate(self._recs)
-               if r.last != key and (r.origin is None or (key - r.origin) % r.every == 0)]
-        if not due:
-            return
-        x = np.asarray(x, dtype=float)
-        b = self._bind_inputs(solver, x, member_pars)
-        for k in due:
-            r = self._recs[k]
-            b.handle.record(k, slot)
-            r.pending.append((b, t))
-            if r.origin is None:
-                r.origin = key
-                r.x = np.array(x[..., r.start:r.stop:r.step])
-            r.last, r.nsys = key, solver.nsys
+    def _first_row(self, r, x, solver):
+        r.x = np.array(x[..., r.start:r.stop:r.step])
 
-    def _flush(self):
-        """Fetch every row still on the device and append it to the series (whole blocks: the rows of
-        a long run are copied once here and once when the blocks are joined)."""
-        for k, r in enumerate(self._recs):
-            if not r.pending:
-                continue
-            bounds = []
-            for b, _ in r.pending:
-                if not any(b is o for o in bounds):
-                    bounds.append(b)
-            fetched = {id(b): b.handle.fetch(k) for b in bounds}
-            if len(bounds) == 1:
-                r.blocks.append(fetched[id(bounds[0])])
-            else:                                        # (several solvers in turn: row by row, in record order)
-                at = {id(b): 0 for b in bounds}
-                for b, _ in r.pending:
-                    r.blocks.append(fetched[id(b)][at[id(b)]:at[id(b)] + 1])
-                    at[id(b)] += 1
-            r.t.extend(t for _, t in r.pending)
-            r.pending.clear()
+    def _no_rows(self, r):
+        return np.zeros((0, r.nsys, r.ncols))
 
     def series(self, per_system=True):
         """name -> (t [rows], x [ncols] or [nsys, ncols], values [rows, nsys, ncols])
         (``per_system=False``: x [ncols], values [rows, ncols])."""
         self._flush()
         out = {}
-        for r in self._recs:
-            if len(r.blocks) != 1:
-                r.blocks = [np.concatenate(r.blocks) if r.blocks else np.zeros((0, r.nsys, r.ncols))]
-            v = r.blocks[0]
+        for r in self._items:
+            v = self._rows(r)
             x = np.zeros(r.ncols) if r.x is None else r.x
             if x.ndim == 2 and (not per_system or (x == x[0]).all()):
                 x = x[0]

@@ -104,12 +104,6 @@ class Simulation(Observed):
         self._actual_timestamp = datetime.datetime.now()
         self._hook = hook
         self._container = None
-        self._probes = None
-        self._recorders = None
-        self._statistics = None
-        self._spectra = None
-        self._extrema = None
-        self._histograms = None
         self._iterator = self.compute()
 
     def _compute_one_step(self, t, fields, pars):
@@ -140,18 +134,8 @@ class Simulation(Observed):
                 t, fields, pars = self._compute_one_step(t, fields, pars)
                 self.i += 1
                 self.t, self.fields, self.parameters = t, fields, pars
-                if self._probes is not None:
-                    self._record_on(self._probes)
-                if self._recorders is not None:
-                    self._record_on(self._recorders)
-                if self._statistics is not None:
-                    self._record_on(self._statistics)
-                if self._spectra is not None:
-                    self._record_on(self._spectra)
-                if self._extrema is not None:
-                    self._record_on(self._extrema)
-                if self._histograms is not None:
-                    self._record_on(self._histograms)
+                for series_set in self._observer_sets():
+                    self._record_on(series_set)
                 for pprocess in self.post_processes:
                     pprocess.function(self)
                 self.stream.emit(self)
@@ -262,9 +246,7 @@ class Simulation(Observed):
 
     def save_recorder(self, name, path):
         """The series of recorder ``name`` as a container directory that ``retrieve_container`` reads."""
-        if self._recorders is None:
-            raise KeyError(name)
-        return self._recorders.save(name, path, self.parameters)
+        return self._observer_set_of("_recorders", name).save(name, path, self.parameters)
 
     def __iter__(self):
         return self.compute()

@@ -19,7 +19,8 @@ object whatever their modes.
 import numpy as np
 
 from . import codegen
-from .observers import ObserverSet, _Bound, discretise  # noqa: F401  (_Bound: the tests build one)
+from .observers import RowItem, RowObserverSet, _is_int, checked_capacity, checked_every, discretise
+from .observers import _Bound  # noqa: F401  (the tests build one)
 
 __all__ = ["SpectrumSet", "MAX_MODES", "DEFAULT_CAPACITY", "MAX_SPECTRA"]
 
@@ -34,19 +35,14 @@ DEFAULT_CAPACITY = 1024
 MAX_SPECTRA = 64
 
 
-class _Spectrum:
+class _Spectrum(RowItem):
     def __init__(self, name, expression, disc, modes, every, capacity):
-        self.name, self.expression, self.disc = name, expression, disc
-        self.modes, self.every, self.capacity = modes, every, capacity
-        self.origin = None           # key of the state of the first row
-        self.last = None             # key of the state of the last row
-        self.pending = []            # rows on the device, in record order: (_Bound, t)
-        self.t, self.blocks = [], []   # fetched: t per row, arrays [rows][nsys][nmodes] in record order
+        super().__init__(name, expression, disc, every)    # (a row: [nsys][nmodes], complex)
+        self.modes, self.capacity = modes, capacity
         self.k = None                # [nmodes] or [nsys][nmodes]
-        self.nsys = 1
 
 
-class SpectrumSet(ObserverSet):
+class SpectrumSet(RowObserverSet):
     """The spectra of one Simulation or Ensemble (``N`` nodes per system) and their series.
 
     Rows are recorded on the device (``record``) and fetched when the series are read (``series``):
@@ -54,23 +50,9 @@ class SpectrumSet(ObserverSet):
     sweep segment of those solvers."""
 
     kind = "spectrum"
-
-    def __init__(self, model, N):
-        super().__init__(model)
-        self.N = int(N)
-        self._specs = []
+    _laid_out = "the spectrum modes were laid out for"
 
     # ---- the set ---------------------------------------------------------------------
-    @property
-    def names(self):
-        return [r.name for r in self._specs]
-
-    def _get(self, name):
-        for r in self._specs:
-            if r.name == name:
-                return r
-        raise KeyError(name)
-
     def _modes(self, name, modes):
         try:
             given = list(modes)
@@ -79,7 +61,7 @@ class SpectrumSet(ObserverSet):
         if not given:
             raise ValueError("spectrum %r: modes is empty" % (name,))
         for m in given:
-            if isinstance(m, (bool, np.bool_)) or not isinstance(m, (int, np.integer)):
+            if not _is_int(m):
                 raise ValueError("spectrum %r: mode %r is not an integer" % (name, m))
         given = [int(m) for m in given]
         if len(given) > MAX_MODES:
@@ -97,109 +79,42 @@ class SpectrumSet(ObserverSet):
         """Validate, lower and append one spectrum (nothing is computed yet)."""
         if name in self.names:
             raise ValueError("a spectrum named %r exists already" % (name,))
-        if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or every < 1:
-            raise ValueError("spectrum %r: every=%r, an integer >= 1 is expected" % (name, every))
+        every = checked_every("spectrum", name, every)
         modes = self._modes(name, modes)
-        if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer))
-                                     or capacity < 1):
-            raise ValueError("spectrum %r: capacity=%r, the ring has one row at least" % (name, capacity))
-        if len(self._specs) >= MAX_SPECTRA:
+        capacity = checked_capacity("spectrum", name, capacity)
+        if len(self._items) >= MAX_SPECTRA:
             raise ValueError("at most %d spectra per simulation (spectrum %r)" % (MAX_SPECTRA, name))
         disc = discretise(self.model, expression)
         codegen.lower_spectra(self.model, [disc])          # (what the C emitter refuses, refused now)
         self._flush()
-        self._specs.append(_Spectrum(name, expression, disc, modes, int(every),
-                                     DEFAULT_CAPACITY if capacity is None else int(capacity)))
-        self._reset()
-
-    def remove(self, name):
-        self._get(name)
-        self._flush()
-        self._specs = [r for r in self._specs if r.name != name]
+        self._items.append(_Spectrum(name, expression, disc, modes, every,
+                                     DEFAULT_CAPACITY if capacity is None else capacity))
         self._reset()
 
     # ---- device side -----------------------------------------------------------------
-    def expressions(self):
-        """The distinct discretised expressions of the set, in the order they were added: spectra of
-        one expression share a case of the spectrum block (and sets that differ only in modes share a
-        code object)."""
-        out = []
-        for r in self._specs:
-            if r.disc not in out:
-                out.append(r.disc)
-        return out
-
     def _lower(self, mask):
         return codegen.lower_spectra(self.model, self.expressions(), parvec_mask=mask)
-
-    def _bind(self, solver):
-        if solver.N != self.N:
-            raise ValueError("the spectrum modes were laid out for %d nodes, the solver has %d"
-                             % (self.N, solver.N))
-        return super()._bind(solver)
 
     def _make_handle(self, solver, code, spec):
         from ._capi import DeviceSpectrum
         exprs = self.expressions()
-        geometry = [(exprs.index(r.disc), len(r.modes), r.capacity) for r in self._specs]
-        return DeviceSpectrum(solver, code, geometry, [r.modes for r in self._specs], len(spec["host_consts"]))
+        geometry = [(exprs.index(r.disc), len(r.modes), r.capacity) for r in self._items]
+        return DeviceSpectrum(solver, code, geometry, [r.modes for r in self._items], len(spec["host_consts"]))
 
-    def due(self, key):
-        """Indices of the spectra that get a row for the state ``key`` (``key`` counts the steps): a
-        spectrum is due at its first state and every ``every`` keys after it, once per key."""
-        return [k for k, r in enumerate(self._specs)
-                if r.last != key and (r.origin is None or (key - r.origin) % r.every == 0)]
+    def _first_row(self, r, x, solver):
+        dx = (x[..., -1] - x[..., 0]) / (self.N - 1)
+        r.k = 2.0 * np.pi * np.asarray(r.modes, dtype=float) / (self.N * np.asarray(dx)[..., None])
 
-    def record(self, solver, slot, t, key, x, member_pars):
-        """Queue a row of every spectrum that is due (``due``): state ``slot`` of ``solver`` (a
-        ``DeviceSolver``).  ``x``: ``[N]`` or ``[nsys][N]``; ``member_pars``: per system, the model's
-        parameter values (the host constants of the expressions are computed from them).  A spectrum
-        that is not due costs nothing on the device."""
-        due = self.due(key)
-        if not due:
-            return
-        x = np.asarray(x, dtype=float)
-        b = self._bind_inputs(solver, x, member_pars)
-        for k in due:
-            r = self._specs[k]
-            b.handle.record(k, slot)
-            r.pending.append((b, t))
-            if r.origin is None:
-                r.origin = key
-                dx = (x[..., -1] - x[..., 0]) / (self.N - 1)
-                r.k = 2.0 * np.pi * np.asarray(r.modes, dtype=float) / (self.N * np.asarray(dx)[..., None])
-            r.last, r.nsys = key, solver.nsys
-
-    def _flush(self):
-        """Fetch every row still on the device and append it to the series."""
-        for k, r in enumerate(self._specs):
-            if not r.pending:
-                continue
-            bounds = []
-            for b, _ in r.pending:
-                if not any(b is o for o in bounds):
-                    bounds.append(b)
-            fetched = {id(b): b.handle.fetch(k) for b in bounds}
-            if len(bounds) == 1:
-                r.blocks.append(fetched[id(bounds[0])])
-            else:                                        # (several solvers in turn: row by row, in record order)
-                at = {id(b): 0 for b in bounds}
-                for b, _ in r.pending:
-                    r.blocks.append(fetched[id(b)][at[id(b)]:at[id(b)] + 1])
-                    at[id(b)] += 1
-            r.t.extend(t for _, t in r.pending)
-            r.pending.clear()
+    def _no_rows(self, r):
+        return np.zeros((0, r.nsys, len(r.modes)), dtype=np.complex128)
 
     def series(self, per_system=True):
         """name -> (t [rows], k [nmodes] or [nsys, nmodes], c [rows, nsys, nmodes] complex128)
         (``per_system=False``: k [nmodes], c [rows, nmodes])."""
         self._flush()
         out = {}
-        for r in self._specs:
-            if len(r.blocks) != 1:
-                r.blocks = [np.concatenate(r.blocks) if r.blocks
-                            else np.zeros((0, r.nsys, len(r.modes)), dtype=np.complex128)]
-            c = r.blocks[0]
+        for r in self._items:
+            c = self._rows(r)
             k = np.zeros(len(r.modes)) if r.k is None else r.k
             if k.ndim == 2 and (not per_system or (k == k[0]).all()):
                 k = k[0]

@@ -17,7 +17,8 @@ lives here, on the host.  ``nodes`` selects the nodes that are returned; every n
 import numpy as np
 
 from . import codegen
-from .observers import ObserverSet, _Bound, discretise  # noqa: F401  (_Bound: the tests build one)
+from .observers import ItemObserverSet, checked_every, checked_nodes, discretise
+from .observers import _Bound  # noqa: F401  (the tests build one)
 
 __all__ = ["StatisticSet", "STATISTIC_KINDS", "MAX_STATISTICS"]
 
@@ -41,7 +42,7 @@ class _Statistic:
         self.nsys = 1
 
 
-class StatisticSet(ObserverSet):
+class StatisticSet(ItemObserverSet):
     """The statistics of one Simulation or Ensemble (``N`` nodes per system) and their accumulators.
 
     Samples are folded on the device (``record``) and the accumulators are fetched when the statistics
@@ -50,53 +51,23 @@ class StatisticSet(ObserverSet):
     grid takes its accumulators along."""
 
     kind = "stat"
-
-    def __init__(self, model, N):
-        super().__init__(model)
-        self.N = int(N)
-        self._stats = []
+    _laid_out = "the statistics were laid out for"
 
     # ---- the set ---------------------------------------------------------------------
-    @property
-    def names(self):
-        return [r.name for r in self._stats]
-
-    def _get(self, name):
-        for r in self._stats:
-            if r.name == name:
-                return r
-        raise KeyError(name)
-
     def add(self, name, expression, stat="mean", every=1, nodes=slice(None)):
         """Validate, lower and append one statistic (nothing is computed yet)."""
         if stat not in STATISTIC_KINDS:
             raise ValueError("unknown kind of statistic stat=%r (one of %s)" % (stat, ", ".join(STATISTIC_KINDS)))
         if name in self.names:
             raise ValueError("a statistic named %r exists already" % (name,))
-        if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or every < 1:
-            raise ValueError("statistic %r: every=%r, an integer >= 1 is expected" % (name, every))
-        if not isinstance(nodes, slice):
-            raise ValueError("statistic %r: nodes=%r, a slice is expected" % (name, nodes))
-        try:
-            window = nodes.indices(self.N)
-        except (TypeError, ValueError) as exc:
-            raise ValueError("statistic %r: nodes=%r: %s" % (name, nodes, exc))
-        if window[2] < 1:
-            raise ValueError("statistic %r: nodes=%r, a step >= 1 is expected" % (name, nodes))
-        if window[1] <= window[0]:
-            raise ValueError("statistic %r: nodes=%r holds no node of a grid of %d" % (name, nodes, self.N))
-        if len(self._stats) >= MAX_STATISTICS:
+        every = checked_every("statistic", name, every)
+        window = checked_nodes("statistic", name, nodes, self.N)
+        if len(self._items) >= MAX_STATISTICS:
             raise ValueError("at most %d statistics per simulation" % MAX_STATISTICS)
         disc = discretise(self.model, expression)
         codegen.lower_statistics(self.model, [disc])       # (what the C emitter refuses, refused now)
         self._flush()
-        self._stats.append(_Statistic(name, expression, disc, stat, int(every), window))
-        self._reset()
-
-    def remove(self, name):
-        self._get(name)
-        self._flush()
-        self._stats = [r for r in self._stats if r.name != name]
+        self._items.append(_Statistic(name, expression, disc, stat, every, window))
         self._reset()
 
     def reset(self, name):
@@ -107,27 +78,13 @@ class StatisticSet(ObserverSet):
         r.n, r.origin, r.where, r.held = 0, None, None, None
 
     # ---- device side -----------------------------------------------------------------
-    def expressions(self):
-        """The distinct discretised expressions of the set, in the order they were added: statistics
-        of one expression share a case of the statistic block."""
-        out = []
-        for r in self._stats:
-            if r.disc not in out:
-                out.append(r.disc)
-        return out
-
     def _lower(self, mask):
         return codegen.lower_statistics(self.model, self.expressions(), parvec_mask=mask)
-
-    def _bind(self, solver):
-        if solver.N != self.N:
-            raise ValueError("the statistics were laid out for %d nodes, the solver has %d" % (self.N, solver.N))
-        return super()._bind(solver)
 
     def _make_handle(self, solver, code, spec):
         from ._capi import DeviceStat
         exprs = self.expressions()
-        geometry = [(exprs.index(r.disc), STATISTIC_KINDS.index(r.kind)) for r in self._stats]
+        geometry = [(exprs.index(r.disc), STATISTIC_KINDS.index(r.kind)) for r in self._items]
         return DeviceStat(solver, code, geometry, len(spec["host_consts"]))
 
     def record(self, solver, slot, t, key, x, member_pars):
@@ -138,14 +95,13 @@ class StatisticSet(ObserverSet):
         that is not due costs nothing on the device.  Accumulators that another solver's handle holds
         (the front end changed its solver), or that came to the host when the set changed, are loaded
         into this solver's handle first: no sample is lost."""
-        due = [k for k, r in enumerate(self._stats)
-               if r.last != key and (r.origin is None or (key - r.origin) % r.every == 0)]
+        due = self.due(key)
         if not due:
             return
         x = np.asarray(x, dtype=float)
         b = self._bind_inputs(solver, x, member_pars)
         for k in due:
-            r = self._stats[k]
+            r = self._items[k]
             if r.n and r.where is not b:
                 if r.where is not None:
                     r.held = r.where.handle.fetch(k)
@@ -161,7 +117,7 @@ class StatisticSet(ObserverSet):
 
     def _flush(self):
         """The accumulators still on a device to the host (the handles are about to be closed)."""
-        for k, r in enumerate(self._stats):
+        for k, r in enumerate(self._items):
             if r.where is not None:
                 r.held = r.where.handle.fetch(k) if r.n else None
                 r.where = None
@@ -171,7 +127,7 @@ class StatisticSet(ObserverSet):
         [ncols], values [ncols]); ``n``: samples folded so far (0: the values are NaN; ``x`` is the grid
         of the first sample ever taken, None before it)."""
         out = {}
-        for k, r in enumerate(self._stats):
+        for k, r in enumerate(self._items):
             if r.n == 0:
                 v = np.full((r.nsys, self.N), np.nan)
             else:

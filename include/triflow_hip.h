@@ -15,7 +15,8 @@
  *            -> tf_model_create, tf_solver_create, tf_set_*, tf_eval, tf_get_F, tf_get_J
  *   seam #2  scheme plugin    scheme(t, fields, dt, pars, hook) -> (t, fields)
  *            triflow/core/schemes.py:101-174 (ROW_general), 523-559 (Theta)
- *            -> tf_step_theta, tf_step_row, tf_step_bdf2 (BDF-2 is new)
+ *            -> tf_step_theta, tf_step_row, tf_step_bdf2, tf_step_erk (BDF-2 and the explicit
+ *               Runge-Kutta steps are new)
  *   seam #3  linear-solver injection  Theta(model, solver=callable(A, b) -> x)
  *            triflow/core/schemes.py:518-521, 557
  *            -> tf_factor, tf_solve
@@ -161,6 +162,26 @@ int tf_step_theta(tf_solver*, int32_t src, int32_t dst, double dt, double theta)
 int tf_step_row(tf_solver*, int32_t src, int32_t dst, double dt, int32_t s,
                 const double* alpha, const double* gamma, const double* b,
                 const double* b_pred, int32_t hook_after, double* err_out);
+/* Explicit Runge-Kutta step (new; the reference has none).  a: [s][s] row major, strictly lower
+ * triangular; b: [s]; d: [s] or NULL, the weights of the error estimate, d = b - b_err with b_err the
+ * weights of the embedded lower-order solution, formed on the host; 1 <= s <= 8.  No Jacobian is
+ * evaluated and nothing is factorised or solved: the factorisation in memory and its counters are left
+ * alone.  The arithmetic, without contraction:
+ *   k_i  = dt * F(U + (((a_i0*k_0) + a_i1*k_1) + ...))        i = 0 ... s-1
+ *   U+   = U + (((b_0*k_0) + b_1*k_1) + ...)
+ *   err  = max over nodes, variables and systems of |((d_0*k_0) + d_1*k_1) + ...|      (NaN wins)
+ * A term whose coefficient is exactly 0.0 is left out of its sum in all three lines, so a non-finite
+ * k_j does not reach a sum it is no part of; a stage without terms evaluates F(U).  err_out (may be NULL)
+ * receives err when d is given, else 0.  hook_after: the Dirichlet list is applied to the result.
+ * src != dst.  The last stage runs in one pass with the update and the estimate (tfk_sweep_f_erk_last)
+ * or, TRIFLOW_ERK_FUSED=0 when the solver is created, as a stage sweep followed by tfk_vec and
+ * tfk_vec_maxabs: the same bits either way. */
+int tf_step_erk(tf_solver*, int32_t src, int32_t dst, double dt, int32_t s,
+                const double* a, const double* b, const double* d, int32_t hook_after,
+                double* err_out);
+/* which form the explicit steps of this solver take (fused: 1 / 0, fixed when the solver is created),
+ * how many tf_step_erk calls it has served, and how many of them ran the fused last stage */
+int tf_erk_info(tf_solver*, int32_t* fused, int64_t* steps, int64_t* fused_steps);
 /* linearly implicit BDF-2 (new, scheme protocol of schemes.py:523-559); the history U_{n-1}
  * is the solver's own: for a caller that owns the solver and steps one trajectory on it */
 int tf_step_bdf2(tf_solver*, int32_t src, int32_t dst, double dt);

@@ -74,6 +74,9 @@ SIGNATURES = {
     "tf_step_row": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32,
                               c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32,
                               c_double_p]),
+    "tf_step_erk": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32,
+                              c_double_p, c_double_p, c_double_p, C.c_int32, c_double_p]),
+    "tf_erk_info": (C.c_int, [C.c_void_p, c_int32_p, c_int64_p, c_int64_p]),
     "tf_step_row_queued": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32,
                                      c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32, C.c_int32]),
     "tf_read_err": (C.c_int, [C.c_void_p, C.c_int32, c_double_p]),
@@ -417,6 +420,28 @@ class DeviceSolver:
                       _dptr(gamma), _dptr(b), _dptr(bp) if bp is not None else None,
                       int(hook_after), C.byref(err) if want_err else None)
         return np.float64(err.value) if (want_err and bp is not None) else None
+
+    def step_erk(self, src, dst, dt, a, b, d=None, hook_after=False, want_err=True):
+        """One explicit Runge-Kutta step (``tf_step_erk``); ``d = b - b_err`` or None.  Returns the
+        error estimate ``max |sum_i d_i k_i|`` when ``d`` is given and wanted, else None."""
+        a, b = _f64(a), _f64(b)
+        s = b.size
+        if a.size != s * s:
+            raise ValueError("step_erk: a is [s][s], b is [s]")
+        dd = _f64(d) if d is not None else None
+        if dd is not None and dd.size != s:
+            raise ValueError("step_erk: d is [s]")
+        err = C.c_double(0.0)
+        self.lib.call("tf_step_erk", self.handle, src, dst, float(dt), s, _dptr(a), _dptr(b),
+                      _dptr(dd) if dd is not None else None, int(hook_after),
+                      C.byref(err) if want_err else None)
+        return np.float64(err.value) if (want_err and dd is not None) else None
+
+    def erk_info(self):
+        """dict(fused, steps, fused_steps): the form of this solver's explicit steps and how many it took."""
+        f, n, nf = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        self.lib.call("tf_erk_info", self.handle, C.byref(f), C.byref(n), C.byref(nf))
+        return dict(fused=bool(f.value), steps=n.value, fused_steps=nf.value)
 
     def step_row_queued(self, src, dst, dt, alpha, gamma, b, b_pred, hook_after=False, err_slot=1):
         """The same step; its embedded error estimate stays on the device (reduction slot ``err_slot``)

@@ -125,6 +125,26 @@ struct TfBerrArgs {               // componentwise backward error of (I - cJ) x 
 // probe of the solve before it (TfBerrArgs::one_node >= 0)
 struct TfStageMonArgs { TfSweepArgs s; TfBerrArgs b; };
 
+// tfk_sweep_f_erk_last / _n: the last stage of an explicit Runge-Kutta step (tf_step_erk) with the update
+// and the error estimate in the same pass.  s: the stage sweep -- fields = U, fscale = dt, and the s.nterms
+// earlier stage vectors k_j (ascending j) that any of the three sums below reads: s.kc[t] is a_{s-1,j} and
+// may be 0.0, then k_j is no part of the stage state and is loaded at the centre node only.  The kernel
+// holds k_last = dt * F(U + sum a k) of its nodes in registers and writes
+//   out = U + (((b[0]*k_0) + b[1]*k_1) + ... + b_last*k_last)                 (TF_VEC_SUM's order)
+//   red = max(red, max over its nodes of |((d[0]*k_0) + ...) + d_last*k_last|)   (with_d; TF_VEC_MAXABS, NaN wins)
+// A term whose coefficient is exactly 0.0 is left out of its sum (b_last / d_last included).  Not in the
+// kernel table: resolved by name (tfb::kernel_lookup), like the histogram kernels; the emulation never
+// launches it.
+struct TfErkTail {
+    double* out;                   // [nvar] planes: the new state (not the planes of s.fields)
+    double* red;                   // one reduction scalar, the bit pattern of a non-negative double
+    double b[TF_MAX_TERMS], d[TF_MAX_TERMS];
+    double b_last, d_last;
+    int with_d;                    // 0: no estimate, red is not touched
+    int pad;
+};
+struct TfErkArgs { TfSweepArgs s; TfErkTail x; };
+
 struct TfVecArgs {                 // elementwise plane algebra
     int64_t n;                     // elements (nvar * plane)
     int nterms;

@@ -171,6 +171,41 @@ __global__ void __launch_bounds__(TF_SWEEP_BLOCK) tfk_sweep_f_stage_rhs_mon(TfSt
     tfk_sweep_body<false, true, false, false, true, TF_STAGE_SEG, 1>(a.s, TF_GID, blockIdx.y);      // (the host launches it for one term)
 }
 
+// The last stage of an explicit Runge-Kutta step (tf_step_erk, TfErkArgs): F at the stage state, the new
+// state U + sum b_j k_j and max |sum d_j k_j| in one pass; dt * F of the last stage stays in registers.
+// The maximum leaves like tfk_berr's: a wavefront shuffle on the bit pattern and one guarded atomic max per
+// wavefront -- integers, so the order of the wavefronts does not show.  The number of stage vectors is a
+// compile-time constant; two kernels, so that the seven-term path (DOPRI5 reads five) does not set the
+// register budget of SSPRK3's, RK4's and BS23's (two and three).  Neither is in the kernel table: the
+// runtime finds them by name.
+__device__ __forceinline__ void tf_erk_reduce(const TfErkTail& x, double m) {
+    if (!x.with_d) return;
+    unsigned long long bits = (unsigned long long)__double_as_longlong(m);
+    if (m != m) bits = 0x7ff8000000000000ull;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(bits, off, 64);
+        bits = o > bits ? o : bits;
+    }
+    if ((threadIdx.x & 63) == 0) tf_raise_max((unsigned long long*)x.red, bits);
+}
+// (Three instantiations, not eight: every one of them evaluates F, and a model's code object is compiled
+// wherever it is first used.  A step with fewer stage vectors runs in the next instantiation up with the
+// other terms' coefficients all zero: such a term is never loaded and is part of no sum.)
+#define TF_ERK_LAST(n) tfk_sweep_body<false, false, false, false, false, TF_SEG, n, true>(a.s, TF_GID, blockIdx.y, &a.x, &m)
+__global__ void __launch_bounds__(TF_SWEEP_BLOCK) tfk_sweep_f_erk_last(TfErkArgs a) {
+    double m = 0.0;
+    TF_ERK_LAST(3);                      // (the host launches it for 0 ... 3 terms: SSPRK3, RK4, BS23)
+    tf_erk_reduce(a.x, m);
+}
+__global__ void __launch_bounds__(TF_SWEEP_BLOCK) tfk_sweep_f_erk_last_n(TfErkArgs a) {
+    double m = 0.0;
+    if (a.s.nterms <= 5) TF_ERK_LAST(5);     // (DOPRI5 reads five)
+    else TF_ERK_LAST(7);
+    tf_erk_reduce(a.x, m);
+}
+#undef TF_ERK_LAST
+
 // grid (nblocks, nvar*nsys): deterministic tree inside the block, one partial per block
 __global__ void __launch_bounds__(256) tfk_diffnorm(TfNormArgs a) {
     double acc = tfk_diffnorm_partial(a, blockIdx.y, blockIdx.x, threadIdx.x, blockDim.x);

@@ -176,8 +176,15 @@ struct TfJUniform {
 // SKIP_JU (TfSweepArgs::ju_valid, the same for the whole launch): the node-independent planes of the
 // value table hold what this sweep would write -- they are neither evaluated nor stored; the other
 // entries, the proportional ones (tf_j_alias) included, are written as ever.
-template <bool WITH_J, bool STAGE, bool THETA, bool BDF, bool STAGE_RHS, int SEG, int NTERMS, bool SKIP_JU>
-TF_DEVICE void tfk_sweep_impl(const TfSweepArgs& a, int pg, int seg) {
+// ERK_LAST (tfk_sweep_f_erk_last, TfErkArgs): the last stage of an explicit Runge-Kutta step.  NTERMS stage
+// vectors, those with kc[t] != 0 form the stage state; next to the window of stage states the thread keeps
+// the raw U and k_j of the rows from the centre to the leading edge (mp + 1 of them), so that the update
+// U + sum b_j k_j and the estimate |sum d_j k_j| of the centre node take no second load of what the window
+// read.  dt * F of the node is not stored.  *xmax: the thread's max |sum d k| (NaN wins and stays).
+template <bool WITH_J, bool STAGE, bool THETA, bool BDF, bool STAGE_RHS, int SEG, int NTERMS, bool SKIP_JU,
+          bool ERK_LAST = false>
+TF_DEVICE void tfk_sweep_impl(const TfSweepArgs& a, int pg, int seg, const TfErkTail* x = nullptr,
+                              double* xmax = nullptr) {
     const TfLayout& L = a.L;
     if (pg >= L.Ptot) return;
     const int e = pg / L.P, p = pg - e * L.P;
@@ -222,14 +229,46 @@ TF_DEVICE void tfk_sweep_impl(const TfSweepArgs& a, int pg, int seg) {
         return u + acc;
     };
 
+    // ERK_LAST: the stage state U + sum_{kc[t] != 0} kc[t] k_t, the terms with a zero coefficient left out
+    // (a wavefront-uniform branch per term); raw[t] = k_t where it was loaded, uraw = U
+    constexpr int NT1 = NTERMS > 0 ? NTERMS : 1;
+    auto lde = [&](int f, int ii, double (&raw)[NT1], double& uraw) -> double {
+        const int64_t q = (int64_t)f * L.plane +
+            ((ii >= 0 && ii < len) ? tf_idx(L, pg, ii) : tf_nbr(L, e, p, len, 0, ii));
+        const double u = a.fields[q];
+        uraw = u;
+#pragma unroll
+        for (int t = 0; t < NTERMS; ++t) raw[t] = a.kc[t] != 0.0 ? a.kx[t][q] : 0.0;
+        double acc = 0.0;
+        bool have = false;
+#pragma unroll
+        for (int t = 0; t < NTERMS; ++t)
+            if (a.kc[t] != 0.0) { const double term = a.kc[t] * raw[t]; acc = have ? acc + term : term; have = true; }
+        return have ? u + acc : u;
+    };
+
     double w[TF_NF][TF_W];
     double wv[STAGE_RHS ? TF_NVAR : 1][TF_W];
+    double eu[ERK_LAST ? TF_NVAR : 1][TF_MP + 1];            // rows centre ... centre + mp: U
+    double ek[ERK_LAST ? NT1 : 1][ERK_LAST ? TF_NVAR : 1][TF_MP + 1];   // ... and the k_t of the stage state
     TfJUniform ju;
     if (STAGE_RHS || (THETA && SKIP_JU)) ju.init(a.parsca, a.dx, L.nsys, e);
 #pragma unroll
     for (int f = 0; f < TF_NF; ++f)
 #pragma unroll
         for (int o = 1; o < TF_W; ++o) {
+            if constexpr (ERK_LAST) {
+                if (f < TF_NVAR) {
+                    double raw[NT1], uraw;
+                    w[f][o] = lde(f, i0 - TF_MP + o - 1, raw, uraw);
+                    if (o > TF_MP) {
+                        eu[f][o - TF_MP] = uraw;
+#pragma unroll
+                        for (int t = 0; t < NTERMS; ++t) ek[t][f][o - TF_MP] = raw[t];
+                    }
+                } else w[f][o] = ld(f, i0 - TF_MP + o - 1);
+                continue;
+            }
             if (STAGE_RHS && f < TF_NVAR) w[f][o] = ld2(f, i0 - TF_MP + o - 1, wv[STAGE_RHS ? f : 0][o]);
             else w[f][o] = ld(f, i0 - TF_MP + o - 1);
         }
@@ -242,6 +281,21 @@ TF_DEVICE void tfk_sweep_impl(const TfSweepArgs& a, int pg, int seg) {
             for (int f = 0; f < TF_NF; ++f) {
 #pragma unroll
                 for (int o = 0; o < TF_W - 1; ++o) w[f][o] = w[f][o + 1];
+                if constexpr (ERK_LAST) {
+                    if (f < TF_NVAR) {
+#pragma unroll
+                        for (int o = 0; o < TF_MP; ++o) {
+                            eu[f][o] = eu[f][o + 1];
+#pragma unroll
+                            for (int t = 0; t < NTERMS; ++t) ek[t][f][o] = ek[t][f][o + 1];
+                        }
+                        double raw[NT1];
+                        w[f][TF_W - 1] = lde(f, i + TF_MP, raw, eu[f][TF_MP]);
+#pragma unroll
+                        for (int t = 0; t < NTERMS; ++t) ek[t][f][TF_MP] = raw[t];
+                    } else w[f][TF_W - 1] = ld(f, i + TF_MP);
+                    continue;
+                }
                 if (STAGE_RHS && f < TF_NVAR) {
 #pragma unroll
                     for (int o = 0; o < TF_W - 1; ++o) wv[STAGE_RHS ? f : 0][o] = wv[STAGE_RHS ? f : 0][o + 1];
@@ -259,6 +313,36 @@ TF_DEVICE void tfk_sweep_impl(const TfSweepArgs& a, int pg, int seg) {
             if (TF_USES_X) xc = a.xcoord[s];
             double Fo[TF_NVAR];
             tf_eval_F(w, par, dx, xc, Fo);
+            if constexpr (ERK_LAST) {
+#pragma unroll
+                for (int v = 0; v < TF_NVAR; ++v) {
+                    const double klast = a.fscale * Fo[v];          // (what tfk_sweep_f_stage would store)
+                    double kk[NT1];
+                    // a k_t the stage state has no part of, but the update or the estimate has: one more load
+#pragma unroll
+                    for (int t = 0; t < NTERMS; ++t)
+                        kk[t] = a.kc[t] != 0.0 ? ek[t][v][0]
+                              : ((x->b[t] != 0.0 || x->d[t] != 0.0) ? tf_ldp(a.kx[t], v, L.plane, off) : 0.0);
+                    double acc = 0.0;
+                    bool have = false;
+#pragma unroll
+                    for (int t = 0; t < NTERMS; ++t)
+                        if (x->b[t] != 0.0) { const double term = x->b[t] * kk[t]; acc = have ? acc + term : term; have = true; }
+                    if (x->b_last != 0.0) { const double term = x->b_last * klast; acc = have ? acc + term : term; have = true; }
+                    tf_stp(x->out, v, L.plane, off, have ? eu[v][0] + acc : eu[v][0]);
+                    if (x->with_d) {
+                        double dac = 0.0;
+                        bool dhave = false;
+#pragma unroll
+                        for (int t = 0; t < NTERMS; ++t)
+                            if (x->d[t] != 0.0) { const double term = x->d[t] * kk[t]; dac = dhave ? dac + term : term; dhave = true; }
+                        if (x->d_last != 0.0) { const double term = x->d_last * klast; dac = dhave ? dac + term : term; dhave = true; }
+                        const double m = tf_abs(dac);
+                        *xmax = (m > *xmax || m != m) ? m : *xmax;
+                    }
+                }
+                continue;
+            }
             if (STAGE_RHS) {
                 double acc[TF_NVAR];
 #pragma unroll
@@ -324,8 +408,13 @@ TF_DEVICE void tfk_sweep_impl(const TfSweepArgs& a, int pg, int seg) {
 
 // One wavefront-uniform branch per launch picks the form (a scalar compare of a kernel argument).
 template <bool WITH_J, bool STAGE = false, bool THETA = false, bool BDF = false, bool STAGE_RHS = false,
-          int SEG = TF_SEG, int NTERMS = 0>
-TF_DEVICE void tfk_sweep_body(const TfSweepArgs& a, int pg, int seg) {
+          int SEG = TF_SEG, int NTERMS = 0, bool ERK_LAST = false>
+TF_DEVICE void tfk_sweep_body(const TfSweepArgs& a, int pg, int seg, const TfErkTail* x = nullptr,
+                              double* xmax = nullptr) {
+    if constexpr (ERK_LAST) {
+        tfk_sweep_impl<false, false, false, false, false, SEG, NTERMS, false, true>(a, pg, seg, x, xmax);
+        return;
+    }
     if constexpr (WITH_J) {
         if (a.ju_valid) { tfk_sweep_impl<WITH_J, STAGE, THETA, BDF, STAGE_RHS, SEG, NTERMS, true>(a, pg, seg); return; }
     }

@@ -94,6 +94,8 @@ tf_solver* make_solver(tf_model* model, int64_t N, int32_t nsys, int32_t periodi
     if (const char* v = getenv("TRIFLOW_FUSE_UPDATE")) s->upd_fuse = atoi(v) != 0;
     if (const char* v = getenv("TRIFLOW_HOOK_IN_PLACE")) s->hook_in_place = atoi(v) != 0;
     if (const char* v = getenv("TRIFLOW_J_UNIFORM_ONCE")) s->ju_once = atoi(v) != 0;
+    s->erk_fused = tfb::is_device_build();               // (the fused last stage is a HIP kernel found by name)
+    if (const char* v = getenv("TRIFLOW_ERK_FUSED")) s->erk_fused = tfb::is_device_build() && atoi(v) != 0;
     s->l1_respike = TF_RESPIKE_MODEL(sp.mp, sp.nvar) && (int64_t)N * nsys >= TF_RESPIKE_MIN_NODES;
     if (const char* v = getenv("TRIFLOW_L1_TWIST")) s->l1_twist = atoi(v) != 0 ? 1 : 0;
     if (const char* v = getenv("TRIFLOW_L1_RESPIKE"))                                   // A/B runs, tests

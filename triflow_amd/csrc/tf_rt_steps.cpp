@@ -67,6 +67,60 @@ void step_row(tf_solver* s, int32_t src, int32_t dst, double dt, int32_t ns, con
     if (hook_after) { s->apply_dirichlet(U, true); s->mark_hooked(dst); }
 }
 
+// Explicit Runge-Kutta step (not in the reference; include/triflow_hip.h, tf_step_erk: the contract).
+//   k_i = dt * F(U + sum_j a_ij k_j),  U+ = U + sum_i b_i k_i,  err = max |sum_i d_i k_i|
+// every sum in ascending j with the exactly-zero coefficients left out.  No Jacobian, no factorisation.
+// Stages 0 ... s-2 are F sweeps into K[i]; the last one is either the same followed by tfk_vec and
+// tfk_vec_maxabs, or (erk_fused) one pass that keeps k_{s-1} in registers and writes U+ and the maximum.
+void step_erk(tf_solver* s, int32_t src, int32_t dst, double dt, int32_t ns, const double* a, const double* b,
+              const double* d, bool hook_after, bool want_err) {
+    require(src != dst, "tf_step_erk: src and dst slots must differ");
+    double* U = s->st(dst);
+    s->slot_written(dst);
+    // The hooked copy of the input goes to a work buffer, not into dst as in the implicit steps: the fused
+    // last stage reads the window of its input while it writes dst.
+    const double* Uin = s->st(src);
+    if (s->ndir > 0 && !s->input_is_hooked(src)) {
+        s->copy(s->Wstage.p, Uin, (size_t)s->vecn() * sizeof(double));
+        s->apply_dirichlet(s->Wstage.p);
+        Uin = s->Wstage.p;
+    }
+    const bool est = d && want_err;
+    const int last = ns - 1;
+    const double* ks[TF_MAX_TERMS];
+    double cs[TF_MAX_TERMS];
+    for (int i = 0; i < ns; ++i) {
+        if (i == last && s->erk_fused) break;
+        int n = 0;
+        for (int j = 0; j < i; ++j)
+            if (a[i * ns + j] != 0.0) { ks[n] = s->K[j].p; cs[n] = a[i * ns + j]; ++n; }
+        s->sweep(Uin, false, n, ks, cs, dt, s->K[i].p);      // (no terms: plain dt * F(U))
+    }
+    if (est) s->zero(s->red.p, sizeof(double));
+    if (s->erk_fused) {
+        // the earlier stage vectors any of the three sums of the last pass reads
+        double ac[TF_MAX_TERMS], bc[TF_MAX_TERMS], dc[TF_MAX_TERMS];
+        int n = 0;
+        for (int j = 0; j < last; ++j) {
+            const double aj = a[last * ns + j], dj = est ? d[j] : 0.0;
+            if (aj != 0.0 || b[j] != 0.0 || dj != 0.0) { ks[n] = s->K[j].p; ac[n] = aj; bc[n] = b[j]; dc[n] = dj; ++n; }
+        }
+        s->sweep_erk_last(Uin, n, ks, ac, bc, est ? dc : nullptr, b[last], est ? d[last] : 0.0, dt, U, 0);
+    } else {
+        int n = 0;
+        for (int j = 0; j < ns; ++j)
+            if (b[j] != 0.0) { ks[n] = s->K[j].p; cs[n] = b[j]; ++n; }
+        s->vec(TF_VEC_SUM, U, Uin, n, ks, cs);                 // U + sum_i b_i k_i
+        if (est) {
+            n = 0;
+            for (int j = 0; j < ns; ++j)
+                if (d[j] != 0.0) { ks[n] = s->K[j].p; cs[n] = d[j]; ++n; }
+            s->vec(TF_VEC_MAXABS, nullptr, nullptr, n, ks, cs, -1, 0);
+        }
+    }
+    if (hook_after) { s->apply_dirichlet(U, true); s->mark_hooked(dst); }
+}
+
 // per system and variable ||state[a] - state[b]||_ord (ord 2 / 0 = max), out[nsys][nvar]
 // with_status: the device-side failure flag and the monitor's worst value come back in the same
 // download (one host wait for a whole step-doubling trial) and are looked at like tf_sync does
@@ -142,6 +196,50 @@ int tf_step_row(tf_solver* s, int32_t src, int32_t dst, double dt, int32_t ns,
         }
         s->check_status();
     }
+    TF_API_END
+}
+
+int tf_step_erk(tf_solver* s, int32_t src, int32_t dst, double dt, int32_t ns, const double* a,
+                const double* b, const double* d, int32_t hook_after, double* err_out) {
+    TF_API_BEGIN
+    require(s && a && b, "null argument");
+    require(ns >= 1 && ns <= TF_MAX_TERMS, "tf_step_erk: 1 <= s <= 8");
+    bool any_b = false, any_d = false;
+    for (int i = 0; i < ns; ++i) {
+        for (int j = i; j < ns; ++j) require(a[i * ns + j] == 0.0, "tf_step_erk: a must be strictly lower triangular");
+        any_b = any_b || b[i] != 0.0;
+        any_d = any_d || (d && d[i] != 0.0);
+    }
+    require(any_b, "tf_step_erk: every weight b_i is zero");
+    require(!(d && err_out) || any_d, "tf_step_erk: every weight d_i of the estimate is zero");
+    // (the step is a linear chain of launches with nothing for the host to decide: always graphable)
+    std::string key = "E|" + std::to_string(src) + ">" + std::to_string(dst) + "|" + bits_of(dt) + "|" +
+        std::to_string(ns) + "|" + std::to_string(hook_after) + "|" + std::to_string(s->ndir) +
+        (s->input_is_hooked(src) ? "h" : "c") + "|" + (d && err_out ? "e" : "-") + (s->erk_fused ? "F" : "U");
+    for (int i = 0; i < ns * ns; ++i) key += bits_of(a[i]) + ",";
+    for (int i = 0; i < ns; ++i) key += bits_of(b[i]) + "," + (d ? bits_of(d[i]) : std::string("-")) + ",";
+    s->erk_prepare(ns);
+    ++s->n_erk_steps;
+    s->run_graphed(key, true, [&] { step_erk(s, src, dst, dt, ns, a, b, d, hook_after != 0, err_out != nullptr); });
+    if (hook_after) s->mark_hooked(dst); else s->slot_written(dst);     // (a replayed graph does not run the host side of the step)
+    if (err_out) {
+        *err_out = 0.0;
+        if (d) {
+            uint64_t bits = 0;
+            tfb::d2h(&bits, s->red.p, sizeof(bits), s->stream);
+            std::memcpy(err_out, &bits, sizeof(double));
+        }
+        s->check_status();
+    }
+    TF_API_END
+}
+
+int tf_erk_info(tf_solver* s, int32_t* fused, int64_t* steps, int64_t* fused_steps) {
+    TF_API_BEGIN
+    require(s, "null solver");
+    if (fused) *fused = s->erk_fused ? 1 : 0;
+    if (steps) *steps = s->n_erk_steps;
+    if (fused_steps) *fused_steps = s->n_erk_fused;
     TF_API_END
 }
 

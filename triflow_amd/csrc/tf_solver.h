@@ -6,7 +6,7 @@
 //                          rescue on longer chunks (tf_solver members)
 //   tf_rt_plan.cpp         models, level plan and memory of a solver (tf_model_*, tf_solver_create ...)
 //   tf_rt_io.cpp           inputs and outputs: states, parameters, hooks, F / J, tf_factor / tf_solve / tf_matvec
-//   tf_rt_steps.cpp        the time-step drivers Theta / Rosenbrock-Wanner / BDF-2 / step doubling
+//   tf_rt_steps.cpp        the time-step drivers Theta / Rosenbrock-Wanner / explicit Runge-Kutta / BDF-2 / step doubling
 //   tf_rt_diag.cpp         counters, monitors, stamps, timing, tf_sync
 //   tf_rt_probe.cpp        device probes (tf_probe_*)   } observers of a resident state slot: tf_observer, at the
 //   tf_rt_record.cpp       device recorders (tf_record_*) } end of this file, is what they share
@@ -410,6 +410,19 @@ struct tf_solver {
     // F, J and rhs = dt*(F - theta*J@U) + U of the theta scheme in one pass
     void sweep_theta(const double* fields, double dt, double theta, double* rhs);
     void spmv(const double* v, double* y, double scale, bool absval = false);
+    // Explicit Runge-Kutta steps (tf_step_erk).  erk_fused: the last stage's pass also writes the new
+    // state and reduces the error estimate (tfk_sweep_f_erk_last / _n, found by name in the model's code
+    // object on first use); off: stage sweep, tfk_vec and tfk_vec_maxabs, the same bits -- the only form
+    // of a back end without the by-name seam (TRIFLOW_ERK_FUSED=0: A/B runs, tests).
+    bool erk_fused = false;
+    tfb::Function* erk_fn[2] = {nullptr, nullptr};
+    int64_t n_erk_steps = 0, n_erk_fused = 0;      // steps taken / of those with the fused last stage (tf_erk_info)
+    void erk_prepare(int nstages);
+    // nterms stage vectors (ascending), their coefficients in the stage state (kc, zeros allowed), in the
+    // update (bc) and in the estimate (dc, NULL: none); b_last / d_last: the last stage's own
+    void sweep_erk_last(const double* fields, int nterms, const double* const* kx, const double* kc,
+                        const double* bc, const double* dc, double b_last, double d_last, double dt,
+                        double* out, int red_slot);
 
     // Right-hand side of Rosenbrock stage i >= 1,  dt*F(U + sum_j alpha_ij k_j) + dt*(J @ sum_j gamma_ij k_j):
     // one pass (tfk_sweep_f_stage_rhs) that evaluates F from the window and multiplies J by the other

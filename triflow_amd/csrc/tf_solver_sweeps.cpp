@@ -72,6 +72,41 @@ void tf_solver::sweep(const double* fields, bool with_j, int nterms, const doubl
     if (with_j) { have_jac = true; have_factor = false; }
 }
 
+// what a step must not do inside a capture: the seventh stage buffer of a 7-stage scheme (K[0..5] are
+// made with the solver) and the lookup of the fused last-stage kernels
+void tf_solver::erk_prepare(int nstages) {
+    // (the fused form keeps the last stage in registers: it has no buffer)
+    const int nbuf = erk_fused ? nstages - 1 : nstages;
+    for (int i = 0; i < nbuf && i < TF_MAX_TERMS; ++i)
+        if (K[i].n < (size_t)vecn()) K[i].alloc((size_t)vecn(), bytes);
+    if (erk_fused && !erk_fn[0]) {
+        erk_fn[0] = tfb::kernel_lookup(model->module, "tfk_sweep_f_erk_last");
+        erk_fn[1] = tfb::kernel_lookup(model->module, "tfk_sweep_f_erk_last_n");
+    }
+}
+
+void tf_solver::sweep_erk_last(const double* fields, int nterms, const double* const* kx, const double* kc,
+                               const double* bc, const double* dc, double b_last, double d_last, double dt,
+                               double* out, int red_slot) {
+    if (nterms < 0 || nterms >= TF_MAX_TERMS) throw std::logic_error("sweep_erk_last: 0 ... 7 stage vectors");
+    if (out == fields) throw std::logic_error("sweep_erk_last: the new state needs planes of its own");
+    TfErkArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.s.nterms = nterms; a.s.fscale = dt;
+    for (int t = 0; t < nterms; ++t) {
+        a.s.kx[t] = kx[t]; a.s.kc[t] = kc[t];
+        a.x.b[t] = bc[t]; a.x.d[t] = dc ? dc[t] : 0.0;
+    }
+    a.s.L = L1; a.s.fields = fields; a.s.helpers = helpers.p; a.s.parvec = parvec.p; a.s.parsca = parsca.p;
+    a.s.dx = dx.p; a.s.xcoord = xcoord.p; a.s.Jv = Jv.p;
+    a.x.out = out; a.x.red = red.p + red_slot;
+    a.x.b_last = b_last; a.x.d_last = dc ? d_last : 0.0; a.x.with_d = dc ? 1 : 0;
+    ++n_erk_fused;                                   // (captured or replayed: counted like a launch)
+    if (mode == TF_DRY) return;
+    tfb::launch_function(erk_fn[nterms <= 3 ? 0 : 1], sweep_gx(), cdiv(L1.M, spec.seg), spec.sweep_block,
+                         &a, sizeof(a), stream);
+}
+
 void tf_solver::sweep_bdf2(const double* fields, bool two_step, double c0, double c1, double* rhs, const double* prev, double* prev_out) {
     TfSweepArgs a;
     std::memset(&a, 0, sizeof(a));

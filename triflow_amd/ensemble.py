@@ -14,7 +14,7 @@ table from rank 0 (``broadcast_table``).
 import numpy as np
 
 from .observers import Observed
-from .tableaux import TABLEAUX
+from .tableaux import ERK_TABLEAUX, TABLEAUX
 
 __all__ = ["Ensemble", "shard_members", "broadcast_table"]
 
@@ -42,7 +42,9 @@ class Ensemble(Observed):
 
     ``fields``: dict name -> array ``[nsys][N]`` (dependent variables and help
     functions); ``x``: ``[N]`` or ``[nsys][N]``; ``pars``: dict name -> scalar,
-    ``[nsys]`` (one value per member) or ``[nsys][N]``.
+    ``[nsys]`` (one value per member) or ``[nsys][N]``.  ``scheme``: fixed steps of ``"ROS2"`` (or
+    another Rosenbrock tableau), ``"Theta"``, ``"BDF2"``, or -- explicit, nothing factorised --
+    ``"SSPRK3"`` / ``"RK4"``.
     """
 
     def __init__(self, model, x, fields, pars, periodic, scheme="ROS2", theta=1.0,
@@ -96,6 +98,8 @@ class Ensemble(Observed):
             s.set_dirichlet(hook.entries(dep, 0.0))
         self.scheme, self.theta = scheme, theta
         self.tab = TABLEAUX.get(scheme)
+        # "SSPRK3" / "RK4": fixed explicit steps (tf_step_erk)
+        self.erk = ERK_TABLEAUX[scheme] if scheme in ("SSPRK3", "RK4") else None
         self.cur, self.t = 0, 0.0
         # BDF-2 with three rotating slots or more: U_{n-1} is still in the slot the previous step
         # started from -- the step reads it there and the history is never copied (tf_step_bdf2_from)
@@ -119,6 +123,8 @@ class Ensemble(Observed):
             self._bdf_prev, self._bdf_dt = src, dt
         elif self.scheme == "BDF2":
             s.step_bdf2(src, dst, dt)
+        elif self.erk is not None:
+            s.step_erk(src, dst, dt, self.erk.a, self.erk.b, None, hook_after=True, want_err=False)
         else:
             s.step_row(src, dst, dt, self.tab.alpha, self.tab.gamma, self.tab.b, None,
                        hook_after=True, want_err=False)

@@ -20,6 +20,7 @@ and arbitrary Python hooks are served.
 * time_stepping ``schemes.py:33-66``    step-doubling wrapper (host logic)
 * scipy_ode    ``schemes.py:430-499``   SciPy integrators fed by ``model.F`` / ``model.J``
 * BDF2         new (named by BASELINE.json, absent from the reference)
+* ERK_general  new: explicit Runge-Kutta, SSPRK3 / RK4 / BS23 / DOPRI5 -> ``tf_step_erk``
 """
 
 import logging
@@ -30,13 +31,14 @@ from functools import wraps
 import numpy as np
 
 from .device import DirichletHook, null_hook, stepper_for
-from .tableaux import TABLEAUX
+from .tableaux import ERK_TABLEAUX, TABLEAUX
 
 log = logging.getLogger(__name__)
 log.addHandler(logging.NullHandler())
 
 __all__ = ["null_hook", "DirichletHook", "time_stepping", "Theta", "ROW_general", "ROS2",
-           "ROS3PRw", "ROS3PRL", "RODASPR", "BDF2", "scipy_ode"]
+           "ROS3PRw", "ROS3PRL", "RODASPR", "BDF2", "scipy_ode",
+           "ERK_general", "SSPRK3", "RK4", "BS23", "DOPRI5"]
 
 
 def _is_device_hook(hook):
@@ -379,6 +381,11 @@ class ROW_general:
             return new_fields
         return None
 
+    def _step_factor(self):
+        """What the controller multiplies ``safety_factor * dt`` by after a trial whose estimate is
+        ``self._err`` (``schemes.py:200-201``: the square root, whatever the order of the tableau)."""
+        return np.sqrt(self._tol / self._err)
+
     def _variable_step(self, t, fields, dt, pars, hook=null_hook):
         """Embedded-error step control (``schemes.py:176-238``)."""
         if self._b_pred is None:
@@ -403,7 +410,7 @@ class ROW_general:
                 log.debug("error: %s", self._err)
                 with np.errstate(divide="ignore"):      # err == 0 -> dt = inf, as in NumPy
                     dt = self._internal_dt = (self._safety_factor * dt
-                                              * np.sqrt(self._tol / self._err))
+                                              * self._step_factor())
             if new_t >= target:
                 self._internal_iter += 1
                 if self._recompute_target:
@@ -454,6 +461,84 @@ def _adaptive_row(name, doc):
 ROS3PRw = _adaptive_row("ROS3PRw", "Third order, 3 stages, adaptive (schemes.py:259-300).")
 ROS3PRL = _adaptive_row("ROS3PRL", "Fourth order, 4 stages, adaptive (schemes.py:303-353).")
 RODASPR = _adaptive_row("RODASPR", "Sixth order, 6 stages, adaptive (schemes.py:356-427).")
+
+
+class ERK_general(ROW_general):
+    """Explicit Runge-Kutta schemes (new; the scheme protocol and the embedded-error step control of
+    :class:`ROW_general`)::
+
+        k_i = dt F(U + sum_j a_ij k_j)      U+ = U + sum_i b_i k_i      err = max |sum_i (b_i - b_err_i) k_i|
+
+    ``a`` is ``[s][s]`` and strictly lower triangular, ``b`` and ``b_err`` are ``[s]`` (``b_err``: the
+    weights of the embedded lower-order solution), ``s <= 8``.  No Jacobian is evaluated and nothing is
+    factorised: for models whose step is set by accuracy or a CFL number, not by stiffness.  A step is
+    ``s`` sweeps on the device (``tf_step_erk``); the hook is applied to the input at ``t`` and to the
+    result at ``t + dt``, never to a stage state.  With ``time_stepping`` the controller is
+    ``ROW_general._variable_step`` with the step-size factor ``(tol / err) ** (1 / order)``, ``order``
+    that of the solution ``b`` propagates."""
+
+    #: nothing is queued ahead of the estimate's read: there is no ``tf_step_erk_queued``
+    QUEUE_NEXT_TRIAL = False
+
+    def __init__(self, model, a, b, b_err=None, order=None, time_stepping=False, tol=None,
+                 max_iter=None, dt_min=None, safety_factor=0.9, recompute_target=True):
+        b = np.asarray(b, dtype=float)
+        a = np.asarray(a, dtype=float)
+        s = b.size
+        if not 1 <= s <= 8:
+            raise ValueError("an explicit scheme has 1 to 8 stages")
+        if a.shape != (s, s) or np.any(np.triu(a) != 0.0):
+            raise ValueError("a must be [s][s] and strictly lower triangular")
+        if b_err is not None and np.shape(b_err) != (s,):
+            raise ValueError("b_err must be [s]")
+        if time_stepping and (b_err is None or order is None):
+            raise ValueError("time stepping needs the embedded weights b_err and the order")
+        zeros = np.zeros((s, s))
+        super().__init__(model, zeros, zeros, b, b_pred=b_err, time_stepping=time_stepping, tol=tol,
+                         max_iter=max_iter, dt_min=dt_min, safety_factor=safety_factor,
+                         recompute_target=recompute_target)
+        self._a, self._order = a, order
+        self._d = None if b_err is None else b - np.asarray(b_err, dtype=float)
+
+    def _device_desc(self):
+        return None          # (the step-doubling wrapper drives an explicit scheme step by step)
+
+    def _step_factor(self):
+        return (self._tol / self._err) ** (1 / self._order)
+
+    def _fixed_step(self, t, fields, dt, pars, hook=null_hook, hook_after=False,
+                    want_err=True, err_slot=None):
+        """``(t + dt, fields, err)`` with ``err = max |sum_i d_i k_i|`` when the tableau has ``b_err``."""
+        device_hook = _is_device_hook(hook)
+
+        def launch(solver, src, dst):
+            return solver.step_erk(src, dst, dt, self._a, self._b, self._d,
+                                   hook_after=hook_after and device_hook,
+                                   want_err=want_err and self._d is not None)
+        new, pars, err = _device_step(self._model, t, fields, pars, hook, launch, dt=dt)
+        if hook_after and not device_hook:
+            new, pars = hook(t + dt, new, pars)
+        return t + dt, new, err
+
+
+def _named_erk(name, doc):
+    tab = ERK_TABLEAUX[name]
+    if tab.b_err is None:
+        def __init__(self, model):
+            ERK_general.__init__(self, model, tab.a, tab.b, order=tab.order)
+    else:
+        def __init__(self, model, tol=1e-1, time_stepping=True, max_iter=None, dt_min=None,
+                     recompute_target=True):
+            ERK_general.__init__(self, model, tab.a, tab.b, b_err=tab.b_err, order=tab.order,
+                                 time_stepping=time_stepping, tol=tol, max_iter=max_iter,
+                                 dt_min=dt_min, recompute_target=recompute_target)
+    return type(name, (ERK_general,), {"__init__": __init__, "__doc__": doc})
+
+
+SSPRK3 = _named_erk("SSPRK3", "Shu-Osher strong-stability-preserving scheme: 3 stages, order 3, fixed step.")
+RK4 = _named_erk("RK4", "The classical Runge-Kutta scheme: 4 stages, order 4, fixed step.")
+BS23 = _named_erk("BS23", "Bogacki-Shampine 3(2): 4 stages, order 3, adaptive.")
+DOPRI5 = _named_erk("DOPRI5", "Dormand-Prince 5(4): 7 stages, order 5, adaptive.")
 
 
 class BDF2:

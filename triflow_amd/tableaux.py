@@ -99,3 +99,48 @@ def _make():
 
 
 TABLEAUX = _make()
+
+
+#: Explicit Runge-Kutta tableaux (``schemes.ERK_general``): ``a`` strictly lower triangular, ``b`` the
+#: weights of the solution that is propagated, ``b_err`` those of the embedded lower-order solution (None:
+#: fixed step only), ``order`` that of the propagated solution.  The literals are exact fractions evaluated
+#: in double.
+ERKTableau = namedtuple("ERKTableau", "a b b_err order")
+
+
+def _make_erk():
+    tabs = {}
+
+    # Shu & Osher (1988): the optimal strong-stability-preserving scheme of three stages
+    tabs["SSPRK3"] = ERKTableau(
+        a=_lower(3, {(1, 0): 1., (2, 0): 1 / 4, (2, 1): 1 / 4}),
+        b=np.array([1 / 6, 1 / 6, 2 / 3]), b_err=None, order=3)
+
+    tabs["RK4"] = ERKTableau(
+        a=_lower(4, {(1, 0): 1 / 2, (2, 1): 1 / 2, (3, 2): 1.}),
+        b=np.array([1 / 6, 1 / 3, 1 / 3, 1 / 6]), b_err=None, order=4)
+
+    # Bogacki & Shampine (1989), 3(2); the fourth stage is F at the new state
+    tabs["BS23"] = ERKTableau(
+        a=_lower(4, {(1, 0): 1 / 2, (2, 1): 3 / 4, (3, 0): 2 / 9, (3, 1): 1 / 3, (3, 2): 4 / 9}),
+        b=np.array([2 / 9, 1 / 3, 4 / 9, 0.]),
+        b_err=np.array([7 / 24, 1 / 4, 1 / 3, 1 / 8]), order=3)
+
+    # Dormand & Prince (1980), 5(4); the seventh stage is F at the new state
+    tabs["DOPRI5"] = ERKTableau(
+        a=_lower(7, {(1, 0): 1 / 5,
+                     (2, 0): 3 / 40, (2, 1): 9 / 40,
+                     (3, 0): 44 / 45, (3, 1): -56 / 15, (3, 2): 32 / 9,
+                     (4, 0): 19372 / 6561, (4, 1): -25360 / 2187, (4, 2): 64448 / 6561,
+                     (4, 3): -212 / 729,
+                     (5, 0): 9017 / 3168, (5, 1): -355 / 33, (5, 2): 46732 / 5247,
+                     (5, 3): 49 / 176, (5, 4): -5103 / 18656,
+                     (6, 0): 35 / 384, (6, 2): 500 / 1113, (6, 3): 125 / 192,
+                     (6, 4): -2187 / 6784, (6, 5): 11 / 84}),
+        b=np.array([35 / 384, 0., 500 / 1113, 125 / 192, -2187 / 6784, 11 / 84, 0.]),
+        b_err=np.array([5179 / 57600, 0., 7571 / 16695, 393 / 640, -92097 / 339200,
+                        187 / 2100, 1 / 40]), order=5)
+    return tabs
+
+
+ERK_TABLEAUX = _make_erk()

@@ -75,7 +75,17 @@ int tf_runtime_info(int32_t* is_device_build, int32_t* device_count);
  * created with device = -1 live, on it */
 int tf_set_device(int32_t ordinal);
 
-/* code object = gfx950 .hsaco image built from the generated per-model source */
+/* code object = gfx950 .hsaco image built from the generated per-model source.
+ *
+ * What a code object must hold.  A model's (tf_model_create): the solver's kernels of the kernel table
+ * (tf_kernel_name), which are the names before "tfk_probe_partial", and the two by-name kernels of the
+ * explicit schemes where those are used.  An observer's (tf_probe_create ... tf_histogram_create): the
+ * kernels of its own kind -- tfk_probe_partial / tfk_probe_final, tfk_record, tfk_stat,
+ * tfk_spectrum_partial / tfk_spectrum_final, tfk_extrema_count / tfk_extrema_write, or (by name)
+ * tfk_hist_partial / tfk_hist_final -- and none of the solver's.  A create call resolves exactly these
+ * names and fails with "kernel missing from code object: NAME" when one is absent, so a code object of
+ * another kind is refused there; what else the image holds is not looked at (an image with every kernel
+ * of the table in it loads everywhere). */
 int tf_model_create(const tf_model_spec* spec, const void* code_object, size_t code_size,
                     tf_model** out);
 /* Second build of the same code object (lower optimisation level): the kernels whose bit
@@ -275,9 +285,9 @@ int tf_kernel_count(void);
 const char* tf_kernel_name(int32_t kernel);
 
 /* ---- device probes: per-step reductions of model expressions on a resident state slot ----------
- * code_object: the model's code object rebuilt with the generated probe block
- * (codegen.lower_probes; built with the solver's parameter layout and sweep segment), of which
- * only tfk_probe_partial / tfk_probe_final are launched.  kinds[nprobe]: 0 sum, 1 mean, 2 integral
+ * code_object: the model's generated source with the generated probe block and csrc/tf_probe.h
+ * (codegen.lower_probes; built with the solver's parameter layout and sweep segment): it holds
+ * tfk_probe_partial / tfk_probe_final.  kinds[nprobe]: 0 sum, 1 mean, 2 integral
  * (np.trapz; periodic: dx * sum), 3 max, 4 min, 5 argmax, 6 argmin (x of the first extremal node);
  * NaN as numpy has it.  nconst: host constants of the probe expressions (codegen spec
  * "host_consts"), set per system by tf_probe_set_consts.  A record is queued on the solver's
@@ -300,8 +310,8 @@ int tf_probe_fetch(tf_probe*, double* out, int64_t max_rows, int64_t* rows);
 int tf_probe_pending(tf_probe*, int64_t* rows);
 
 /* ---- device recorders: decimated space-time series of model expressions on a resident state slot ----
- * code_object: the model's code object rebuilt with the generated record block (codegen.lower_records;
- * built with the solver's parameter layout and sweep segment), of which only tfk_record is launched.
+ * code_object: the model's generated source with the generated record block and csrc/tf_record.h
+ * (codegen.lower_records; built with the solver's parameter layout and sweep segment): it holds tfk_record.
  * geometry[nrec][6]: the expression of the block (recorders may share one), pool (0 sample, 1 max,
  * 2 min, 3 mean), start, stop, step of the window of nodes (0 <= start < stop <= N, step >= 1) and
  * the rows of the recorder's device ring (>= 2: two halves).
@@ -325,9 +335,9 @@ int tf_record_fetch(tf_record*, int32_t which, double* out, int64_t max_rows, in
 int tf_record_pending(tf_record*, int32_t which, int64_t* rows);
 
 /* ---- device statistics: per-node statistics over time of model expressions on a resident state slot ----
- * code_object: the model's code object rebuilt with the generated statistic block
- * (codegen.lower_statistics; built with the solver's parameter layout and sweep segment), of which only
- * tfk_stat is launched.  geometry[nstat][2]: the expression of the block (statistics may share one; the
+ * code_object: the model's generated source with the generated statistic block and csrc/tf_stat.h
+ * (codegen.lower_statistics; built with the solver's parameter layout and sweep segment): it holds
+ * tfk_stat.  geometry[nstat][2]: the expression of the block (statistics may share one; the
  * expressions are numbered in the order the statistics first use them: 0, then at most one more) and
  * the kind: 0 mean, 1 var (running mean and sum of squared deviations M2; the variance is M2 / n),
  * 2 max, 3 min (NaN as numpy has it), 4 argmax, 5 argmin (the extremum and the t of the first sample
@@ -352,9 +362,9 @@ int tf_stat_fetch(tf_stat*, int32_t which, double* out);
 int tf_stat_load(tf_stat*, int32_t which, const double* in);
 
 /* ---- device spectra: Fourier amplitudes of model expressions on a resident state slot ----
- * code_object: the model's code object rebuilt with the generated spectrum block (codegen.lower_spectra;
- * built with the solver's parameter layout and sweep segment), of which only tfk_spectrum_partial and
- * tfk_spectrum_final are launched.  geometry[nspec][3]: the expression of the block (spectra may share
+ * code_object: the model's generated source with the generated spectrum block and csrc/tf_spectrum.h
+ * (codegen.lower_spectra; built with the solver's parameter layout and sweep segment): it holds
+ * tfk_spectrum_partial and tfk_spectrum_final.  geometry[nspec][3]: the expression of the block (spectra may share
  * one; the expressions are numbered in the order the spectra first use them), the number of modes
  * (1 ... 64) and the rows of the spectrum's ring in device memory.  The modes themselves (each 0 ... N/2)
  * are data of the handle: set_modes before the first record.  A record is queued on the solver's stream
@@ -377,9 +387,9 @@ int tf_spectrum_fetch(tf_spectrum*, int32_t which, double* out, int64_t max_rows
 int tf_spectrum_pending(tf_spectrum*, int32_t which, int64_t* rows);
 
 /* ---- device extrema: crests and troughs of model expressions on a resident state slot ----
- * code_object: the model's code object rebuilt with the generated extrema block (codegen.lower_extrema;
- * built with the solver's parameter layout and sweep segment), of which only tfk_extrema_count and
- * tfk_extrema_write are launched.  geometry[next][4]: the expression of the block (observers may share
+ * code_object: the model's generated source with the generated extrema block and csrc/tf_extrema.h
+ * (codegen.lower_extrema; built with the solver's parameter layout and sweep segment): it holds
+ * tfk_extrema_count and tfk_extrema_write.  geometry[next][4]: the expression of the block (observers may share
  * one; the expressions are numbered in the order the observers first use them), the kind (0: max, 1: min),
  * max_count (1 ... 8192) and the rows of the observer's ring in device memory (0: 1024 rows, or what 32 MB
  * hold; a single row that is larger is refused).  thresholds[next]: a maximum counts when it is greater, a
@@ -404,9 +414,9 @@ int tf_extrema_fetch(tf_extrema*, int32_t which, double* out, int64_t max_rows, 
 int tf_extrema_pending(tf_extrema*, int32_t which, int64_t* rows);
 
 /* ---- device histograms: value distributions of model expressions on a resident state slot ----
- * code_object: the model's code object rebuilt with the generated histogram block
- * (codegen.lower_histograms; built with the solver's parameter layout and sweep segment).  Only such a code
- * object holds tfk_hist_partial and tfk_hist_final: they are not in the kernel table (tf_kernel_name), are
+ * code_object: the model's generated source with the generated histogram block and csrc/tf_histogram.h
+ * (codegen.lower_histograms; built with the solver's parameter layout and sweep segment).  It
+ * holds tfk_hist_partial and tfk_hist_final: they are not in the kernel table (tf_kernel_name), are
  * resolved by name here and are not covered by tf_timing_get.  geometry[nhist][6]: the expression of the
  * block (histograms may share one; the expressions are numbered in the order the histograms first use
  * them), the number of bins (1 ... 256), the rows of the histogram's ring in device memory and the window

@@ -21,7 +21,7 @@ BUILD = os.path.join(HERE, "_build")
 
 def _deps_stamp():
     parts = []
-    for d, names in ((CSRC, ("tf_args.h", "tf_math.h", "tf_kernels.h", "tf_crs.h", "tf_solver.h", *RUNTIME_SOURCES,
+    for d, names in ((CSRC, ("tf_args.h", "tf_math.h", "tf_layout.h", "tf_kernels.h", "tf_crs.h", "tf_solver.h", *RUNTIME_SOURCES,
                              "tf_backend.h")),
                      (HERE, ("tf_backend_emu.cpp",)),
                      (os.path.join(ROOT, "include"), ("triflow_hip.h",))):

@@ -14,7 +14,7 @@ from triflow_amd import codegen, probes
 from triflow_amd.extrema import EXTREMA_KINDS
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-HEADERS = ("tf_args.h", "tf_math.h", "tf_kernels.h", "tf_node.h", "tf_extrema.h")
+HEADERS = ("tf_args.h", "tf_math.h", "tf_layout.h", "tf_kernels.h", "tf_node.h", "tf_extrema.h")
 
 
 def build(model, exprs, parvec_mask=0):

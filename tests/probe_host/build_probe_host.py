@@ -12,7 +12,7 @@ from tests.observer_host import common
 from triflow_amd import codegen, probes
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-HEADERS = ("tf_args.h", "tf_math.h", "tf_kernels.h", "tf_node.h", "tf_probe.h")
+HEADERS = ("tf_args.h", "tf_math.h", "tf_layout.h", "tf_kernels.h", "tf_node.h", "tf_probe.h")
 
 
 def build(model, exprs, reductions, parvec_mask=0):

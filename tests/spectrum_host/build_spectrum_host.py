@@ -14,7 +14,7 @@ from tests.observer_host import common
 from triflow_amd import codegen, probes
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-HEADERS = ("tf_args.h", "tf_math.h", "tf_kernels.h", "tf_node.h", "tf_spectrum.h")
+HEADERS = ("tf_args.h", "tf_math.h", "tf_layout.h", "tf_kernels.h", "tf_node.h", "tf_spectrum.h")
 
 
 def build(model, exprs, parvec_mask=0):

@@ -174,16 +174,14 @@ def test_record_block_and_spec():
         assert "    case %d: return %s" % (k, expr) in block
 
 
-def test_the_record_kernel_follows_the_table_and_every_code_object_has_it():
+def test_the_record_kernel_follows_the_table():
     import re
     from triflow_amd import compilers
     with open(compilers.CSRC + "/tf_args.h") as f:
         text = f.read()
     assert re.search(r'TF_KERNEL_NAMES_RECORD \{ "tfk_record" \}', text)
     assert re.search(r"TFK_PROBE_FINAL,\s*TFK_RECORD, TFK_COUNT", text)
-    with open(compilers.CSRC + "/tf_record.h") as f:
-        assert "#define TF_NREC 0" in f.read()
-    assert "tf_record.h" in compilers._SKELETON and "tf_rt_record.cpp" in compilers.RUNTIME_SOURCES
+    assert "tf_rt_record.cpp" in compilers.RUNTIME_SOURCES      # (the code objects: tests/test_observer_objects.py)
 
 
 # ---- validation --------------------------------------------------------------------------------

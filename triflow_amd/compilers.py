@@ -66,17 +66,17 @@ def extra_flags(*flags):
 RUNTIME_SOURCES = ("tf_rt_plan.cpp", "tf_rt_io.cpp", "tf_rt_steps.cpp", "tf_rt_diag.cpp",
                    "tf_solver_sweeps.cpp", "tf_solver_linear.cpp", "tf_rt_probe.cpp", "tf_rt_record.cpp",
                    "tf_rt_stat.cpp", "tf_rt_spectrum.cpp", "tf_rt_extrema.cpp", "tf_rt_histogram.cpp")
-_SKELETON = ("tf_args.h", "tf_math.h", "tf_kernels.h", "tf_crs.h", "tf_coop_hip.h", "tf_cr2_hip.h", "tf_cr3_hip.h",
-             "tf_cr_io.h",
-             "tf_node.h", "tf_probe.h", "tf_record.h", "tf_stat.h", "tf_spectrum.h", "tf_extrema.h",
-             "tf_histogram.h", "tf_entry_hip.h")
+#: the headers a model's own code object is compiled from ...
+_SKELETON = ("tf_args.h", "tf_math.h", "tf_layout.h", "tf_kernels.h", "tf_crs.h", "tf_coop_hip.h", "tf_cr2_hip.h",
+             "tf_cr3_hip.h", "tf_cr_io.h", "tf_entry_hip.h")
+#: ... and an observer's, by kind: the layout, the node core and the kind's own header, which ends its unit
+_OBSERVER_SKELETON = {kind: ("tf_args.h", "tf_math.h", "tf_layout.h", "tf_node.h", header) for kind, header in (
+    ("probe", "tf_probe.h"), ("record", "tf_record.h"), ("stat", "tf_stat.h"), ("spectrum", "tf_spectrum.h"),
+    ("extrema", "tf_extrema.h"), ("histogram", "tf_histogram.h"))}
 _TU_HEAD = ('#include <hip/hip_runtime.h>\n'
             '#define TF_DEVICE __device__ __forceinline__\n'
             '%s'
             '#include "tf_math.h"\n')
-
-#: kinds of observer whose kernels are not named ``tfk_<kind>*``
-_OBSERVER_KERNELS = {"histogram": "hist"}
 _TU_TAIL = '#include "tf_kernels.h"\n#include "tf_entry_hip.h"\n'
 
 
@@ -87,10 +87,12 @@ def _hipcc():
     return exe
 
 
-def _skeleton_stamp():
+def _skeleton_stamp(kind=None, csrc=CSRC):
+    """Hash of the headers (read from ``csrc``) that a model's own code object is compiled from, or with
+    ``kind`` an observer's of that kind."""
     parts = []
-    for name in _SKELETON:
-        with open(os.path.join(CSRC, name), "rb") as f:
+    for name in _OBSERVER_SKELETON[kind] if kind else _SKELETON:
+        with open(os.path.join(csrc, name), "rb") as f:
             parts.append(f.read())
     return codegen.source_hash(*parts)
 
@@ -140,10 +142,8 @@ def resource_usage(hsaco_path):
 
 def _compile_code_object(model, source, tag, hsaco, observer=None):
     """hipcc on the generated translation unit -> ``hsaco`` (+ source and resource table next to it).
-    ``observer``: the unit carries an observer's block (build_observer_code_object) and this is its kind,
-    "probe", "record", "stat", "spectrum", "extrema" or "histogram" (its kernels: ``tfk_hist*``): only the kernels
-    ``tfk_<kind>*`` of that object are ever launched, so
-    there is no second build for the spill gate -- one of them that spills is refused instead."""
+    ``observer``: the unit is an observer's (build_observer_code_object) and this is its kind: there is no
+    second build for the spill gate -- a kernel of the object that spills is refused instead."""
     global BUILD_COUNT
     BUILD_COUNT += 1
     hip = os.path.join(CACHE_DIR, "model_%s.hip" % tag)
@@ -154,7 +154,8 @@ def _compile_code_object(model, source, tag, hsaco, observer=None):
         f.write(source)
     os.replace(hip_tmp, hip)
     tmp = hsaco + ".%d.tmp" % os.getpid()
-    log.info("hipcc: compiling stencil + solver kernels for %s", model._diff_eqs)
+    log.info("hipcc: compiling %s for %s", "the %s kernels" % observer if observer else "stencil + solver kernels",
+             model._diff_eqs)
 
     def compile_with(flags, out):
         cmd = [_hipcc(), *flags, "-I", CSRC, "--genco", "--no-gpu-bundle-output",
@@ -168,14 +169,11 @@ def _compile_code_object(model, source, tag, hsaco, observer=None):
     flags = list(HIPCC_FLAGS)
     usage = compile_with(flags, tmp)
     spilled = sorted(k for k, u in usage.items() if u.get("ScratchSize", 0) > 0)
-    if observer:
-        spilled = [k for k in spilled if k.startswith("tfk_" + _OBSERVER_KERNELS.get(observer, observer))]
-        if spilled:
-            os.remove(tmp)
-            raise codegen.UnsupportedExpression(
-                "the %s kernels (%s) need more registers than a wavefront has: "
-                "use fewer or simpler %ss" % (observer, ", ".join(spilled),
-                                               {"stat": "statistic"}.get(observer, observer)))
+    if observer and spilled:
+        os.remove(tmp)
+        raise codegen.UnsupportedExpression(
+            "the %s kernels (%s) need more registers than a wavefront has: "
+            "use fewer or simpler %ss" % (observer, ", ".join(spilled), {"stat": "statistic"}.get(observer, observer)))
     alt_flags, alt_usage = None, None
     alt = hsaco[:-len(".hsaco")] + ".alt.hsaco"
     if spilled and "-O1" not in flags and "-O0" not in flags \
@@ -196,10 +194,10 @@ def _compile_code_object(model, source, tag, hsaco, observer=None):
             os.replace(alt + ".%d.tmp" % os.getpid(), alt)
     meta = os.path.join(CACHE_DIR, "model_%s.json" % tag)
     with open(meta + ".%d.tmp" % os.getpid(), "w") as f:
-        json.dump(dict(equations=list(model._diff_eqs), flags=flags, kernels=usage,
+        json.dump(dict(equations=list(model._diff_eqs), kind=observer or "model", flags=flags, kernels=usage,
                        alt_flags=alt_flags, alt_kernels=spilled if alt_flags else [],
                        alt_usage={k: alt_usage[k] for k in spilled} if alt_usage else {},
-                       skeleton=_skeleton_stamp(), hipcc=hipcc_version()), f, indent=1)
+                       skeleton=_skeleton_stamp(observer), hipcc=hipcc_version()), f, indent=1)
     os.replace(meta + ".%d.tmp" % os.getpid(), meta)
     os.replace(tmp, hsaco)
     evict_stale_cache()
@@ -287,18 +285,17 @@ def build_code_object(model, parvec_mask=0, seg=None, sweep_block=None):
 
 
 def build_observer_code_object(model, block, kind, parvec_mask=0, seg=8, sweep_block=256):
-    """The model's translation unit followed by the block of an observer of ``kind`` "probe"
-    (codegen.lower_probes), "record" (codegen.lower_records), "stat" (codegen.lower_statistics),
-    "spectrum" (codegen.lower_spectra), "extrema" (codegen.lower_extrema) or "histogram"
-    (codegen.lower_histograms: the one kind whose kernels, ``tfk_hist*``, no other code object holds) ->
-    path of the cached code object, of which only the kernels ``tfk_<kind>*`` are launched.  Same parameter
-    layout and sweep segment as the solver's own code object: the observer's kernels read that solver's
-    planes and parameter slots."""
-    if kind not in ("probe", "record", "stat", "spectrum", "extrema", "histogram"):
+    """The code object of an observer of ``kind`` "probe" (``block`` from codegen.lower_probes), "record"
+    (lower_records), "stat" (lower_statistics), "spectrum" (lower_spectra), "extrema" (lower_extrema) or
+    "histogram" (lower_histograms) -> path of the cached code object.  Its unit is the model's generated
+    body, the block and the kind's header (``csrc/tf_<kind>.h``): it holds the kernels of that kind and no
+    others, none of the solver's.  Same parameter layout and sweep segment as the solver's own code object:
+    the observer's kernels read that solver's planes and parameter slots."""
+    if kind not in _OBSERVER_SKELETON:
         raise ValueError("unknown kind of observer %r" % (kind,))
     body, _ = codegen.lower_model(model, parvec_mask=parvec_mask, seg=seg, sweep_block=sweep_block)
-    source = _TU_HEAD % "" + body + block + _TU_TAIL
-    tag = codegen.source_hash(source, _skeleton_stamp(), " ".join(HIPCC_FLAGS), hipcc_version(), kind, "elf")
+    source = _TU_HEAD % "" + body + block + '#include "%s"\n' % _OBSERVER_SKELETON[kind][-1]
+    tag = codegen.source_hash(source, _skeleton_stamp(kind), " ".join(HIPCC_FLAGS), hipcc_version(), kind, "elf")
     os.makedirs(CACHE_DIR, exist_ok=True)
     hsaco = os.path.join(CACHE_DIR, "model_%s.hsaco" % tag)
     _build_locked(model, source, tag, hsaco, observer=kind)
@@ -325,12 +322,15 @@ def hipcc_version():
 
 
 def evict_stale_cache(keep=()):
-    """Remove cached code objects that were built against another version of the kernel
-    skeleton (``csrc/*.h``) or another hipcc: they can never be selected again (the tag
-    hashes both), they only make the cache -- which travels with the package -- grow."""
+    """Remove cached code objects that were built against another version of the headers of their
+    kind (``_SKELETON``, ``_OBSERVER_SKELETON``) or another hipcc: they can never be selected again (the
+    tag hashes both), they only make the cache -- which travels with the package -- grow.  An entry
+    that does not say its kind is older than the kinds' own stamps: stale."""
     if not os.path.isdir(CACHE_DIR):
         return 0
-    stamp, ver, removed = _skeleton_stamp(), hipcc_version(), 0
+    stamps = {kind: _skeleton_stamp(kind) for kind in _OBSERVER_SKELETON}
+    stamps["model"] = _skeleton_stamp()
+    ver, removed = hipcc_version(), 0
     for name in os.listdir(CACHE_DIR):
         if not (name.startswith("model_") and name.endswith(".json")):
             continue
@@ -340,7 +340,7 @@ def evict_stale_cache(keep=()):
                 meta = json.load(f)
         except (OSError, ValueError):
             continue
-        if meta.get("skeleton") == stamp and meta.get("hipcc") == ver:
+        if meta.get("skeleton") == stamps.get(meta.get("kind"), "") and meta.get("hipcc") == ver:
             continue
         if os.path.basename(base) in keep:
             continue

@@ -498,8 +498,8 @@ struct TfExtremaArgs : TfNodeArgs {
 // tfk_probe_partial, counts in unsigned 32-bit integers in LDS, one set of nbins + 3 per workgroup leaves
 // with plain stores; tfk_hist_final: grid (nsys, ceil((nbins + 3) / 64)), 1024 threads, sums the sets of its
 // system and writes row `row` of the ring as doubles (exact: a count is below 2^53).  Integers throughout: any order gives the same row.
-// These two kernels are not in the kernel table below: only a code object of kind "histogram" holds them,
-// and the runtime resolves them by name (tfb::kernel_lookup).
+// These two kernels are not in the kernel table below: the runtime resolves them by name
+// (tfb::kernel_lookup) in a code object of kind "histogram".
 #define TF_HIST_MAX_BINS 256
 struct TfHistArgs : TfNodeArgs {
     int which;                     // expression of the histogram block (tf_eval_hist's first argument)
@@ -524,9 +524,11 @@ static_assert(sizeof(TfStatArgs) == 136, "TfStatArgs changed its layout");
 static_assert(sizeof(TfSpectrumArgs) == 144, "TfSpectrumArgs changed its layout");
 static_assert(sizeof(TfExtremaArgs) == 152, "TfExtremaArgs changed its layout");
 
-// Kernel table: index = launch id used by the runtime, name = entry point in
-// the per-model code object (tf_entry_hip.h).  New entries go at the end: the
-// launch ids and the timing-mask bits of the others stay put.
+// Kernel table: index = launch id used by the runtime, name = entry point in a code object of the
+// model: the ids before TFK_PROBE_PARTIAL in the model's own (tf_entry_hip.h), an observer's from there
+// on in the code object of its kind (tf_probe.h ...).  A module resolves the range of its kind
+// (tfb::module_resolve).  New entries go at the end: the launch ids and the timing-mask bits of the
+// others stay put.
 enum TfKernel {
     TFK_SWEEP_F = 0, TFK_SWEEP_FJ, TFK_SPMV, TFK_VEC, TFK_VEC_MAXABS, TFK_PERM, TFK_DIRICHLET,
     TFK_L1_FACTOR, TFK_L1_SOLVE, TFK_L1_ASM_MAT, TFK_L1_ASM_RHS, TFK_L1_BACKSUB,
@@ -551,7 +553,7 @@ enum TfKernel {
 // ... continued: the kernels of the recorders (ids TFK_RECORD ...), a table of their own
 #define TF_KERNEL_NAMES_RECORD { "tfk_record" }
 // ... and the launch ids after TFK_COUNT, with a table of their own as well: the kernel of the statistics.
-// TFK_TOTAL is the number of kernels of a code object: what the runtime sizes and loops by.
+// TFK_TOTAL is the number of kernels of the table: what the runtime sizes its per-kernel arrays by.
 // After it, the kernels of the spectra (TF_KERNEL_NAMES_SPECTRUM), then those of the extrema
 // (TF_KERNEL_NAMES_EXTREMA).
 enum TfKernelMore { TFK_STAT = TFK_COUNT, TFK_SPECTRUM_PARTIAL, TFK_SPECTRUM_FINAL,

@@ -31,8 +31,15 @@ void d2h(void* dst, const void* src, size_t bytes, Stream* s);     // synchronou
 void d2d(void* dst, const void* src, size_t bytes, Stream* s);
 
 Module* module_load(const void* image, size_t bytes);
+// Resolves the kernels first ... first + count - 1 of the kernel table (tf_args.h) in a loaded code object:
+// what a code object of its kind has to hold.  One of them missing throws std::runtime_error("kernel missing
+// from code object: NAME"); what else the image holds is not looked at.  kernel_block, launch and
+// launch_timed throw for a kernel that was not resolved.  A back end without code objects need not define
+// it: tf_rt_plan.cpp holds a weak definition that does nothing.
+void module_resolve(Module* m, int first, int count);
 // kernels whose bit is set in `mask` (kernel table index) are taken from a second build of the
-// same translation unit (the per-kernel optimisation gate of compilers.py)
+// same translation unit (the per-kernel optimisation gate of compilers.py); bits of kernels that were
+// not resolved are ignored
 void module_add_alternate(Module* m, const void* image, size_t bytes, uint64_t mask);
 void module_unload(Module* m);
 
@@ -54,9 +61,8 @@ void launch_timed(Module* m, int kernel, unsigned gx, unsigned gy, unsigned bloc
                   const void* args, size_t arg_bytes, Stream* s, Event* start, Event* stop,
                   unsigned lds_bytes = 0);
 
-// Kernels that are not in the kernel table (tf_args.h): only some code objects hold them (the device
-// histograms' "histogram" kind), so they are resolved by name once the code object is loaded and launched
-// through the handle.  kernel_lookup throws std::runtime_error when the code object has no such kernel;
+// Kernels that are not in the kernel table (tf_args.h) -- the device histograms', the last stage of the
+// explicit schemes -- are resolved by name once the code object is loaded and launched through the handle.  kernel_lookup throws std::runtime_error when the code object has no such kernel;
 // the handle lives as long as the module.  A back end without the seam need not define either:
 // tf_rt_histogram.cpp holds weak definitions that throw "not supported by this back end".
 struct Function;

@@ -22,7 +22,13 @@ static void check(hipError_t err, const char* what) {
 }
 #define TF_HIP(call) check((call), #call)
 
-struct Module { hipModule_t mod; hipFunction_t fn[TFK_TOTAL]; hipModule_t alt = nullptr; };
+// fn[k]: null for a kernel that was not resolved (module_resolve)
+struct Module { hipModule_t mod; hipFunction_t fn[TFK_TOTAL] = {}; hipModule_t alt = nullptr; };
+static hipFunction_t resolved(Module* m, int kernel) {
+    if (kernel < 0 || kernel >= TFK_TOTAL || !m->fn[kernel])
+        throw std::runtime_error(std::string("kernel not resolved in this code object: ") + tf_kernel_entry(kernel));
+    return m->fn[kernel];
+}
 struct Stream { hipStream_t s; };
 struct Event { hipEvent_t e; };
 
@@ -170,14 +176,14 @@ Module* module_load(const void* image, size_t) {
         delete m;
         check(err, "hipModuleLoadData (is the code object built for this GPU, gfx950?)");
     }
-    for (int k = 0; k < TFK_TOTAL; ++k) {
-        err = hipModuleGetFunction(&m->fn[k], m->mod, tf_kernel_entry(k));
-        if (err != hipSuccess) {
-            (void)hipModuleUnload(m->mod);
-            delete m;
+    return m;
+}
+void module_resolve(Module* m, int first, int count) {
+    for (int k = first; k < first + count; ++k)
+        if (hipModuleGetFunction(&m->fn[k], m->mod, tf_kernel_entry(k)) != hipSuccess) {
+            m->fn[k] = nullptr;
             throw std::runtime_error(std::string("kernel missing from code object: ") + tf_kernel_entry(k));
         }
-    }
     // Debug aid for compiler bisection: TF_ALT_HSACO=<file> TF_ALT_MASK=<bits> takes
     // the kernels whose bit is set from a second build of the same model.
     if (const char* alt = getenv("TF_ALT_HSACO")) {
@@ -191,19 +197,18 @@ Module* module_load(const void* image, size_t) {
                 hipModule_t am;
                 if (hipModuleLoadData(&am, img.data()) == hipSuccess)
                     for (int k = 0; k < TFK_TOTAL; ++k)
-                        if ((mask >> k) & 1ul) (void)hipModuleGetFunction(&m->fn[k], am, tf_kernel_entry(k));
+                        if (((mask >> k) & 1ul) && m->fn[k]) (void)hipModuleGetFunction(&m->fn[k], am, tf_kernel_entry(k));
             }
         }
         if (f) fclose(f);
     }
-    return m;
 }
 void module_add_alternate(Module* m, const void* image, size_t, uint64_t mask) {
     if (!m || !mask) return;
     if (m->alt) throw std::runtime_error("module_add_alternate: one alternate build per model");
     check(hipModuleLoadData(&m->alt, image), "hipModuleLoadData (alternate build)");
     for (int k = 0; k < TFK_TOTAL; ++k)
-        if ((mask >> k) & 1ull) {
+        if (((mask >> k) & 1ull) && m->fn[k]) {
             if (hipModuleGetFunction(&m->fn[k], m->alt, tf_kernel_entry(k)) != hipSuccess)
                 throw std::runtime_error(std::string("kernel missing from the alternate code object: ") + tf_kernel_entry(k));
         }
@@ -225,7 +230,7 @@ void stream_sync(Stream* s) { TF_HIP(hipStreamSynchronize(s->s)); }
 
 unsigned kernel_block(Module* m, int kernel) {
     int v = 0;
-    TF_HIP(hipFuncGetAttribute(&v, HIP_FUNC_ATTRIBUTE_MAX_THREADS_PER_BLOCK, m->fn[kernel]));
+    TF_HIP(hipFuncGetAttribute(&v, HIP_FUNC_ATTRIBUTE_MAX_THREADS_PER_BLOCK, resolved(m, kernel)));
     return (unsigned)v;
 }
 
@@ -234,7 +239,7 @@ void launch(Module* m, int kernel, unsigned gx, unsigned gy, unsigned block,
     size_t size = arg_bytes;
     void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, const_cast<void*>(args),
                       HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-    TF_HIP(hipModuleLaunchKernel(m->fn[kernel], gx, gy, 1, block, 1, 1, lds_bytes, s->s, nullptr, config));
+    TF_HIP(hipModuleLaunchKernel(resolved(m, kernel), gx, gy, 1, block, 1, 1, lds_bytes, s->s, nullptr, config));
 }
 
 void launch_timed(Module* m, int kernel, unsigned gx, unsigned gy, unsigned block,
@@ -244,7 +249,7 @@ void launch_timed(Module* m, int kernel, unsigned gx, unsigned gy, unsigned bloc
     void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, const_cast<void*>(args),
                       HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
     // hipExtModuleLaunchKernel takes the global size in work-items
-    TF_HIP(hipExtModuleLaunchKernel(m->fn[kernel], gx * block, gy, 1, block, 1, 1, lds_bytes, s->s,
+    TF_HIP(hipExtModuleLaunchKernel(resolved(m, kernel), gx * block, gy, 1, block, 1, 1, lds_bytes, s->s,
                                     nullptr, config, start->e, stop->e, 0));
 }
 

@@ -7,12 +7,6 @@
 #include "tf_coop_hip.h"
 #include "tf_cr2_hip.h"
 #include "tf_cr3_hip.h"
-#include "tf_probe.h"
-#include "tf_record.h"
-#include "tf_stat.h"
-#include "tf_spectrum.h"
-#include "tf_extrema.h"
-#include "tf_histogram.h"          // (tfk_hist_*: only in a code object with a histogram block)
 
 #define TF_GID ((int)(blockIdx.x * blockDim.x + threadIdx.x))
 
@@ -226,101 +220,6 @@ __global__ void __launch_bounds__(256) tfk_diffnorm(TfNormArgs a) {
             unsigned long long bits = (unsigned)*a.status;
             tail[0] = __longlong_as_double((long long)bits);
             tail[1] = *a.mon;
-        }
-    }
-}
-
-// ---- device probes (tf_probe.h): grid (nsys * nblk, nseg), one thread per segment of a level-1 chunk ------
-// The chunk walks of a workgroup reduce through a 64-lane shuffle tree (every lane ends with the same
-// value: the partner sums are the same two operands) and LDS across the four wavefronts, in a fixed
-// order; one (value, index) pair per workgroup, probe and system leaves with plain stores.  No atomics on
-// floating-point data: the series are bitwise reproducible.
-__device__ __forceinline__ TfProbeAcc tf_probe_wave(int kind, TfProbeAcc r) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const TfProbeAcc o{__shfl_xor(r.v, off, 64), __shfl_xor(r.i, off, 64)};
-        r = tf_probe_combine(kind, r, o);
-    }
-    return r;
-}
-__global__ void __launch_bounds__(256) tfk_probe_partial(TfProbeArgs a) {
-    if constexpr (TF_NPROBE > 0) {
-        const int e = blockIdx.x / a.nblk, blk = blockIdx.x - e * a.nblk, sg = blockIdx.y;
-        const int p = blk * 256 + threadIdx.x;
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        TfProbeAcc acc[TF_NPROBE_A];
-        if (p < a.L.P) tf_probe_walk(a, e, p, sg, acc);
-        else {
-#pragma unroll
-            for (int k = 0; k < TF_NPROBE; ++k) acc[k] = tf_probe_identity(tf_probe_kind[k]);
-        }
-        __shared__ double lv[4][TF_NPROBE_A], li[4][TF_NPROBE_A];
-#pragma unroll
-        for (int k = 0; k < TF_NPROBE; ++k) {
-            const TfProbeAcc r = tf_probe_wave(tf_probe_kind[k], acc[k]);
-            if (lane == 0) { lv[wave][k] = r.v; li[wave][k] = r.i; }
-        }
-        __syncthreads();
-        if (threadIdx.x < TF_NPROBE) {
-            const int k = threadIdx.x, kind = tf_probe_kind[k];
-            TfProbeAcc r{lv[0][k], li[0][k]};
-            for (int w = 1; w < 4; ++w) r = tf_probe_combine(kind, r, TfProbeAcc{lv[w][k], li[w][k]});
-            double* out = a.partial + (((int64_t)e * TF_NPROBE + k) * a.nseg * a.nblk + sg * a.nblk + blk) * 2;
-            out[0] = r.v;
-            out[1] = r.i;
-        }
-    }
-}
-// grid (nsys), 256 threads: wavefront w reduces probes w, w + 4, ... of one system -- the
-// partials in a fixed order, strided over the lanes, then the shuffle tree -- and lane 0 writes the finished
-// value into row cursor[0] of the ring.  The row cursor lives in device memory: every workgroup reads it,
-// and the last of them to be done with the row (an integer counter) advances it -- a replayed launch
-// writes the next row, not the one it was captured with.
-__global__ void __launch_bounds__(256) tfk_probe_final(TfProbeArgs a) {
-    if constexpr (TF_NPROBE > 0) {
-        const int e = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        const TfLayout& L = a.L;
-        const int row = *(volatile int*)&a.cursor[0];
-        const int nb = a.nblk * a.nseg;
-        for (int k = wave; k < TF_NPROBE; k += 4) {
-            const int kind = tf_probe_kind[k];
-            const double* part = a.partial + ((int64_t)e * TF_NPROBE + k) * nb * 2;
-            TfProbeAcc r = tf_probe_identity(kind);
-            // (eight partials per lane loaded before they are combined, in the same order: one at a time, the
-            // loop was a chain of HBM round trips, 6.9 us at config 3)
-            for (int b0 = lane; b0 < nb; b0 += 64 * 8) {
-                TfProbeAcc v[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int b = b0 + 64 * j;
-                    v[j] = b < nb ? TfProbeAcc{part[2 * b], part[2 * b + 1]} : tf_probe_identity(kind);
-                }
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if (b0 + 64 * j < nb) r = tf_probe_combine(kind, r, v[j]);
-            }
-            r = tf_probe_wave(kind, r);
-            if (lane == 0) {
-                double xnode = 0.0;
-                if ((kind == TF_PROBE_ARGMAX || kind == TF_PROBE_ARGMIN) && r.i >= 0.0 && r.i < (double)L.N) {
-                    int p, i;
-                    tf_locate(L, (int)r.i, p, i);
-                    xnode = a.xcoord[tf_idx(L, e * L.P + p, i)];
-                }
-                const double* end = a.ends + ((int64_t)e * TF_NPROBE + k) * 2;
-                const double f0 = kind == TF_PROBE_INTEGRAL ? end[0] : 0.0;
-                const double fN1 = kind == TF_PROBE_INTEGRAL ? end[1] : 0.0;
-                const double val = tf_probe_finish(kind, r, L.N, L.periodic, a.dx[e], f0, fN1, xnode);
-                if (row < a.capacity) a.ring[((int64_t)row * L.nsys + e) * TF_NPROBE + k] = val;
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            __threadfence();
-            if (atomicAdd(&a.cursor[1], 1) == L.nsys - 1) {
-                atomicExch(&a.cursor[1], 0);
-                atomicExch(&a.cursor[0], row < a.capacity ? row + 1 : row);
-            }
         }
     }
 }

@@ -8,8 +8,8 @@
 // threshold; the neighbours wrap on a periodic grid, the end nodes of any other grid are never extrema
 // (scipy.signal.argrelextrema with np.greater / np.less, mode "wrap" / "clip").  A NaN compares false, so a
 // NaN neighbour disqualifies a node; a plateau of equal values is not reported.  The generated block defines
-// TF_NEXT, TF_NEXT_HC, TF_EXT_USES_X and tf_eval_extrema before this header is read; every other code object
-// compiles the no-op defaults below (every code object holds every kernel of the table, tf_args.h).
+// TF_NEXT, TF_NEXT_HC, TF_EXT_USES_X and tf_eval_extrema before this header is read: it is the tail of an
+// extrema code object's translation unit and of no other.
 //
 // In the partition-interleaved layout node order is not thread order, so a row is an ordered stream
 // compaction in two passes: tfk_extrema_count counts the extrema of every chunk, tfk_extrema_write scans the
@@ -22,14 +22,6 @@
 // the file.
 #pragma once
 #include "tf_node.h"
-
-#ifndef TF_NEXT
-#define TF_NEXT 0
-#define TF_NEXT_HC 0
-#define TF_EXT_USES_X 0
-TF_DEVICE double tf_eval_extrema(int, const double (&)[TF_NVAR + TF_NH][2 * TF_MP + 1], const double*,
-                                 const double*, double, double) { return 0.0; }
-#endif
 
 // Is the node with the value vc between vl and vr an extremum?  Finite: vc - vc is 0.0 for a finite value and
 // NaN for an infinity or a NaN.  A NaN among vl, vr fails its comparison.
@@ -132,18 +124,16 @@ TF_DEVICE int tf_ext_wave_scan(int v, int lane) {
 // wavefront sit over neighbouring chunks, so every load of the state is 512 contiguous bytes.  The count of
 // every chunk (0 for the threads past the last chunk) and the sum of the workgroup leave with plain stores.
 extern "C" __global__ void __launch_bounds__(256) tfk_extrema_count(TfExtremaArgs a) {
-    if constexpr (TF_NEXT > 0) {
-        __shared__ int part[4];
-        const int e = blockIdx.x / a.nblk, blk = blockIdx.x - e * a.nblk;
-        const int p = blk * 256 + threadIdx.x;
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        const int c = p < a.L.P ? tf_extrema_count(a, e, p) : 0;
-        a.counts[((int64_t)e * a.nblk + blk) * 256 + threadIdx.x] = c;
-        const int s = tf_ext_wave_sum(c);
-        if (lane == 0) part[wave] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) a.sums[(int64_t)e * a.nblk + blk] = (part[0] + part[1]) + (part[2] + part[3]);
-    }
+    __shared__ int part[4];
+    const int e = blockIdx.x / a.nblk, blk = blockIdx.x - e * a.nblk;
+    const int p = blk * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = p < a.L.P ? tf_extrema_count(a, e, p) : 0;
+    a.counts[((int64_t)e * a.nblk + blk) * 256 + threadIdx.x] = c;
+    const int s = tf_ext_wave_sum(c);
+    if (lane == 0) part[wave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) a.sums[(int64_t)e * a.nblk + blk] = (part[0] + part[1]) + (part[2] + part[3]);
 }
 
 // Same grid.  The first wavefront adds the sums of the workgroups of its own system, those before this
@@ -154,35 +144,33 @@ extern "C" __global__ void __launch_bounds__(256) tfk_extrema_count(TfExtremaArg
 // by value, from the host's count of the rows: the launch is queued on the solver's stream between the
 // steps, never inside a captured graph (a replay would write every row where it was captured).
 extern "C" __global__ void __launch_bounds__(256) tfk_extrema_write(TfExtremaArgs a) {
-    if constexpr (TF_NEXT > 0) {
-        __shared__ int part[4];
-        __shared__ int head[2];
-        const int e = blockIdx.x / a.nblk, blk = blockIdx.x - e * a.nblk;
-        const int p = blk * 256 + threadIdx.x;
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        // (before the barrier below: a is the launch's argument, the same for every thread, so the whole
-        // workgroup leaves or none of it does -- a condition that differs between threads must not go here)
-        if (a.row < 0 || a.row >= a.capacity) return;
-        const int c = a.counts[((int64_t)e * a.nblk + blk) * 256 + threadIdx.x];
-        const int incl = tf_ext_wave_scan(c, lane);
-        if (lane == 63) part[wave] = incl;
-        if (wave == 0) {
-            const int* sums = a.sums + (int64_t)e * a.nblk;
-            int before = 0, all = 0;
-            for (int b = lane; b < a.nblk; b += 64) {
-                const int s = sums[b];
-                all += s;
-                if (b < blk) before += s;
-            }
-            before = tf_ext_wave_sum(before);
-            all = tf_ext_wave_sum(all);
-            if (lane == 0) { head[0] = before; head[1] = all; }
+    __shared__ int part[4];
+    __shared__ int head[2];
+    const int e = blockIdx.x / a.nblk, blk = blockIdx.x - e * a.nblk;
+    const int p = blk * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // (before the barrier below: a is the launch's argument, the same for every thread, so the whole
+    // workgroup leaves or none of it does -- a condition that differs between threads must not go here)
+    if (a.row < 0 || a.row >= a.capacity) return;
+    const int c = a.counts[((int64_t)e * a.nblk + blk) * 256 + threadIdx.x];
+    const int incl = tf_ext_wave_scan(c, lane);
+    if (lane == 63) part[wave] = incl;
+    if (wave == 0) {
+        const int* sums = a.sums + (int64_t)e * a.nblk;
+        int before = 0, all = 0;
+        for (int b = lane; b < a.nblk; b += 64) {
+            const int s = sums[b];
+            all += s;
+            if (b < blk) before += s;
         }
-        __syncthreads();
-        int offset = head[0] + (incl - c);
-        for (int w = 0; w < wave; ++w) offset += part[w];
-        if (blk == 0 && threadIdx.x == 0) tf_extrema_row(a, e)[0] = (double)head[1];
-        if (p < a.L.P && c > 0 && offset < a.max_count) tf_extrema_store(a, e, p, offset);
+        before = tf_ext_wave_sum(before);
+        all = tf_ext_wave_sum(all);
+        if (lane == 0) { head[0] = before; head[1] = all; }
     }
+    __syncthreads();
+    int offset = head[0] + (incl - c);
+    for (int w = 0; w < wave; ++w) offset += part[w];
+    if (blk == 0 && threadIdx.x == 0) tf_extrema_row(a, e)[0] = (double)head[1];
+    if (p < a.L.P && c > 0 && offset < a.max_count) tf_extrema_store(a, e, p, offset);
 }
 #endif

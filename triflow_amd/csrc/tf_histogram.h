@@ -8,9 +8,10 @@
 // edges[i + 1], the last bin also v == edges[nbins]; below, above and NaN are counted apart.  That is
 // np.histogram(v, bins=edges)[0] for the values it accepts.
 //
-// Unlike the other observers' kernels, tfk_hist_partial and tfk_hist_final are not in the kernel table:
-// this header is empty unless the generated histogram block (TF_NHIST, TF_NHIST_HC, TF_HIST_USES_X,
-// tf_eval_hist) precedes it, so every other code object comes out without them.
+// The generated histogram block defines TF_NHIST, TF_NHIST_HC, TF_HIST_USES_X and tf_eval_hist before this
+// header is read: it is the tail of a histogram code object's translation unit and of no other.  Unlike the
+// other observers' kernels, tfk_hist_partial and tfk_hist_final are not in the kernel table (tf_args.h): the
+// runtime finds them by name.
 //
 // The classification (of one value, and of the values of a segment at once), the window test and the walk
 // of one thread (on the node window the histograms share with the other observers, tf_node.h) are what the
@@ -19,7 +20,6 @@
 #pragma once
 #include "tf_node.h"
 
-#ifdef TF_NHIST
 // Counter of the value v among nbins + 3: 0 ... nbins - 1 the bins, nbins: v < edges[0], nbins + 1:
 // v > edges[nbins], nbins + 2: NaN.  Comparisons only (so -0.0 is 0.0 and the infinities go below / above):
 // inside, a bisection for the last edge that is <= v, kept below nbins so that v == edges[nbins] lands
@@ -169,4 +169,3 @@ extern "C" __global__ void __launch_bounds__(TF_HIST_FINAL_BLOCK) tfk_hist_final
     }
 }
 #endif
-#endif  // TF_NHIST

@@ -26,14 +26,9 @@
 // emulation build under tests/emu/, which runs these very functions thread by
 // thread on the CPU; the product library never contains that build.
 #pragma once
-#include "tf_args.h"
 
-#ifndef TF_DEVICE
-#error "define TF_DEVICE (e.g. __device__ __forceinline__) before including tf_kernels.h"
-#endif
+#include "tf_layout.h"          // TF_W, TF_NF, tf_len ... tf_locate
 
-#define TF_W (2 * TF_MP + 1)
-#define TF_NF (TF_NVAR + TF_NH)
 #define TF_B2 (TF_MP * TF_NVAR)          // block size of the reduced (interface) systems
 #ifndef TF_UOUT_FACT
 #define TF_UOUT_FACT 0                   // (generated for the models that take the factored form: TfUOut)
@@ -82,46 +77,6 @@
 #else
 #define TF_WG_BARRIER() do {} while (0)
 #endif
-
-// ------------------------------------------------------------------- layout
-TF_DEVICE int tf_len(const TfLayout& L, int p) { return L.mbase + (p < L.rem ? 1 : 0); }
-TF_DEVICE int tf_start(const TfLayout& L, int p) { return p * L.mbase + (p < L.rem ? p : L.rem); }
-TF_DEVICE int64_t tf_idx(const TfLayout& L, int pg, int i) { return (int64_t)i * L.Ptot + pg; }
-// Element of plane k at byte offset off8 = 8 * tf_idx(...): the plane's base stays in scalar
-// registers and the lane offset is 32 bits wide (global_load/store with saddr: no 64-bit address
-// arithmetic per access).  A plane is smaller than 4 GB (tf_solver_create checks).
-TF_DEVICE unsigned tf_off8(const TfLayout& L, int pg, int i) { return (unsigned)tf_idx(L, pg, i) * 8u; }
-TF_DEVICE double tf_ldp(const double* base, int64_t k, int64_t plane, unsigned off8) {
-    return *(const double*)((const char*)(base + k * plane) + off8);
-}
-TF_DEVICE void tf_stp(double* base, int64_t k, int64_t plane, unsigned off8, double v) {
-    *(double*)((char*)(base + k * plane) + off8) = v;
-}
-
-// element of the node `d` places after node i of chunk (e, p); wraps or clamps
-// at the ends of the system exactly like the ghost cells of
-// triflow/core/compilers.py:257-264.  Needs |d| <= mbase.
-TF_DEVICE int64_t tf_nbr(const TfLayout& L, int e, int p, int len, int i, int d) {
-    int ii = i + d;
-    int pp = p;
-    if (ii < 0) {
-        if (p > 0) { pp = p - 1; ii += tf_len(L, pp); }
-        else if (L.periodic) { pp = L.P - 1; ii += tf_len(L, pp); }
-        else ii = 0;
-    } else if (ii >= len) {
-        if (p < L.P - 1) { pp = p + 1; ii -= len; }
-        else if (L.periodic) { pp = 0; ii -= len; }
-        else ii = len - 1;
-    }
-    return tf_idx(L, e * L.P + pp, ii);
-}
-
-// node index -> (chunk, row)
-TF_DEVICE void tf_locate(const TfLayout& L, int g, int& p, int& i) {
-    int big = L.rem * (L.mbase + 1);
-    if (g < big) { p = g / (L.mbase + 1); i = g - p * (L.mbase + 1); }
-    else { int h = g - big; p = L.rem + h / L.mbase; i = h - (h / L.mbase) * L.mbase; }
-}
 
 // element addresses in the NEXT solver level, which is stored either as
 // partition-interleaved planes (s2 = tf_idx of the separator there) or, below

@@ -5,9 +5,10 @@
 // for one thread, whatever the thread does with the values.  An observer supplies its walk (which nodes,
 // in which order, folded how), its kernels and its ring; TfNodeArgs (tf_args.h) leads its arguments.
 //
-// Compiled by hipcc into every code object and by g++ into the host harnesses of the test suite
-// (tests/probe_host, tests/record_host), after tf_kernels.h (tf_idx, tf_nbr).
+// Compiled by hipcc into every observer's code object, and into none of the solver's, and by g++ into the
+// host harnesses of the test suite (tests/probe_host, tests/record_host ...).
 #pragma once
+#include "tf_layout.h"          // tf_idx, tf_nbr
 
 // A value and the natural node index it was met at (a double: exact for any node count a plane can hold).
 struct TfNodeAcc { double v, i; };

@@ -4,25 +4,17 @@
 // the per-node body tf_eval_probe (same emitter as tf_eval_F: the per-node values are the bits
 // the reference's lambdified NumPy code computes), and a reduction over the nodes of a system.
 // The generated probe block defines TF_NPROBE, TF_NPROBE_HC, TF_PROBE_USES_X, tf_probe_kind[]
-// and tf_eval_probe before this header is read; a model code object without probes compiles
-// the no-op defaults below (every code object holds every kernel of the table, tf_args.h).
+// and tf_eval_probe before this header is read: it is the tail of a probe code object's
+// translation unit and of no other.
 //
-// This file holds what the host harness of the test suite (tests/probe_host/) also compiles
-// with g++: the reduction algebra and the walk of one thread along its chunk, on the node window
-// that the probes share with the recorders (tf_node.h).  The shuffle / LDS trees and the ring
-// hand-over are in tf_entry_hip.h (tfk_probe_partial, tfk_probe_final).
+// The reduction algebra and the walk of one thread along its chunk, on the node window that the
+// probes share with the other observers (tf_node.h), are what the host harness of the test suite
+// (tests/probe_host/) also compiles with g++; the kernels, with the shuffle / LDS trees and the ring
+// hand-over, are at the end of the file.
 #pragma once
 #include "tf_node.h"
 
-#ifndef TF_NPROBE
-#define TF_NPROBE 0
-#define TF_NPROBE_HC 0
-#define TF_PROBE_USES_X 0
-static constexpr int tf_probe_kind[1] = {0};
-TF_DEVICE void tf_eval_probe(const double (&)[TF_NVAR + TF_NH][2 * TF_MP + 1], const double*,
-                             const double*, double, double, double*) {}
-#endif
-#define TF_NPROBE_A (TF_NPROBE > 0 ? TF_NPROBE : 1)
+#define TF_NPROBE_A TF_NPROBE      // extent of a thread's accumulators (the host harness names it)
 
 // Running state of one reduction: the value and, for argmax / argmin, the natural node index it was
 // met at.  Sums ignore the index.
@@ -40,7 +32,7 @@ TF_DEVICE TfProbeAcc tf_probe_identity(int kind) {
 // b after a: the reduction of the two.  Maxima / minima follow numpy: NaN wins (max, min: tf_node_extremum),
 // the first NaN wins (argmax, argmin), among equal values the smallest node index wins.  For every
 // kind but the sums the result does not depend on the order of the operands, so any tree gives
-// numpy's answer; the sums are added in a fixed order (the trees of tf_entry_hip.h).
+// numpy's answer; the sums are added in a fixed order (the trees of the kernels below).
 TF_DEVICE TfProbeAcc tf_probe_combine(int kind, TfProbeAcc a, TfProbeAcc b) {
     if (tf_probe_summed(kind)) return {a.v + b.v, 0.0};
     const bool anan = a.v != a.v, bnan = b.v != b.v;
@@ -71,7 +63,7 @@ TF_DEVICE double tf_probe_finish(int kind, TfProbeAcc r, int N, int periodic, do
 // natural nodes 0 and N-1 also leave f there in a.ends (the integral's end correction).  NODES (the host
 // harness of the tests only): every node's values also go to nodes[(k * nsys + e) * N + natural index].
 template <bool NODES = false>
-TF_DEVICE void tf_probe_walk(const TfProbeArgs& a, int e, int p, int sg, TfProbeAcc (&acc)[TF_NPROBE_A],
+TF_DEVICE void tf_probe_walk(const TfProbeArgs& a, int e, int p, int sg, TfProbeAcc (&acc)[TF_NPROBE],
                              double* nodes = nullptr) {
     const TfLayout& L = a.L;
     const int len = tf_len(L, p);
@@ -79,7 +71,7 @@ TF_DEVICE void tf_probe_walk(const TfProbeArgs& a, int e, int p, int sg, TfProbe
     const int i0 = sg * TF_PROBE_SEG;
     TfNodeWindow<TF_NPROBE_HC, TF_PROBE_USES_X> W(a, e);
 #pragma unroll
-    for (int k = 0; k < TF_NPROBE_A; ++k) acc[k] = tf_probe_identity(tf_probe_kind[k]);
+    for (int k = 0; k < TF_NPROBE; ++k) acc[k] = tf_probe_identity(tf_probe_kind[k]);
     if (i0 >= len) return;
     W.prime(p, len, i0);
 #pragma unroll
@@ -87,7 +79,7 @@ TF_DEVICE void tf_probe_walk(const TfProbeArgs& a, int e, int p, int sg, TfProbe
         const int i = i0 + j;
         if (i >= len) break;
         W.advance(p, len, i);
-        double v[TF_NPROBE_A];
+        double v[TF_NPROBE];
         tf_eval_probe(W.w, W.par, W.hc, W.dx, W.xc, v);
         const double gi = (double)(gstart + i);
 #pragma unroll
@@ -102,3 +94,96 @@ TF_DEVICE void tf_probe_walk(const TfProbeArgs& a, int e, int p, int sg, TfProbe
         }
     }
 }
+
+#if defined(__HIPCC__)
+// tfk_probe_partial: grid (nsys * nblk, nseg), 256 threads, one thread per segment of a level-1 chunk.
+// The chunk walks of a workgroup reduce through a 64-lane shuffle tree (every lane ends with the same
+// value: the partner sums are the same two operands) and LDS across the four wavefronts, in a fixed
+// order; one (value, index) pair per workgroup, probe and system leaves with plain stores.  No atomics on
+// floating-point data: the series are bitwise reproducible.
+TF_DEVICE TfProbeAcc tf_probe_wave(int kind, TfProbeAcc r) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const TfProbeAcc o{__shfl_xor(r.v, off, 64), __shfl_xor(r.i, off, 64)};
+        r = tf_probe_combine(kind, r, o);
+    }
+    return r;
+}
+extern "C" __global__ void __launch_bounds__(256) tfk_probe_partial(TfProbeArgs a) {
+    const int e = blockIdx.x / a.nblk, blk = blockIdx.x - e * a.nblk, sg = blockIdx.y;
+    const int p = blk * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    TfProbeAcc acc[TF_NPROBE];
+    if (p < a.L.P) tf_probe_walk(a, e, p, sg, acc);
+    else {
+#pragma unroll
+        for (int k = 0; k < TF_NPROBE; ++k) acc[k] = tf_probe_identity(tf_probe_kind[k]);
+    }
+    __shared__ double lv[4][TF_NPROBE], li[4][TF_NPROBE];
+#pragma unroll
+    for (int k = 0; k < TF_NPROBE; ++k) {
+        const TfProbeAcc r = tf_probe_wave(tf_probe_kind[k], acc[k]);
+        if (lane == 0) { lv[wave][k] = r.v; li[wave][k] = r.i; }
+    }
+    __syncthreads();
+    if (threadIdx.x < TF_NPROBE) {
+        const int k = threadIdx.x, kind = tf_probe_kind[k];
+        TfProbeAcc r{lv[0][k], li[0][k]};
+        for (int w = 1; w < 4; ++w) r = tf_probe_combine(kind, r, TfProbeAcc{lv[w][k], li[w][k]});
+        double* out = a.partial + (((int64_t)e * TF_NPROBE + k) * a.nseg * a.nblk + sg * a.nblk + blk) * 2;
+        out[0] = r.v;
+        out[1] = r.i;
+    }
+}
+// grid (nsys), 256 threads: wavefront w reduces probes w, w + 4, ... of one system -- the
+// partials in a fixed order, strided over the lanes, then the shuffle tree -- and lane 0 writes the finished
+// value into row cursor[0] of the ring.  The row cursor lives in device memory: every workgroup reads it,
+// and the last of them to be done with the row (an integer counter) advances it -- a replayed launch
+// writes the next row, not the one it was captured with.
+extern "C" __global__ void __launch_bounds__(256) tfk_probe_final(TfProbeArgs a) {
+    const int e = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const TfLayout& L = a.L;
+    const int row = *(volatile int*)&a.cursor[0];
+    const int nb = a.nblk * a.nseg;
+    for (int k = wave; k < TF_NPROBE; k += 4) {
+        const int kind = tf_probe_kind[k];
+        const double* part = a.partial + ((int64_t)e * TF_NPROBE + k) * nb * 2;
+        TfProbeAcc r = tf_probe_identity(kind);
+        // (eight partials per lane loaded before they are combined, in the same order: one at a time, the
+        // loop was a chain of HBM round trips, 6.9 us at config 3)
+        for (int b0 = lane; b0 < nb; b0 += 64 * 8) {
+            TfProbeAcc v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int b = b0 + 64 * j;
+                v[j] = b < nb ? TfProbeAcc{part[2 * b], part[2 * b + 1]} : tf_probe_identity(kind);
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (b0 + 64 * j < nb) r = tf_probe_combine(kind, r, v[j]);
+        }
+        r = tf_probe_wave(kind, r);
+        if (lane == 0) {
+            double xnode = 0.0;
+            if ((kind == TF_PROBE_ARGMAX || kind == TF_PROBE_ARGMIN) && r.i >= 0.0 && r.i < (double)L.N) {
+                int p, i;
+                tf_locate(L, (int)r.i, p, i);
+                xnode = a.xcoord[tf_idx(L, e * L.P + p, i)];
+            }
+            const double* end = a.ends + ((int64_t)e * TF_NPROBE + k) * 2;
+            const double f0 = kind == TF_PROBE_INTEGRAL ? end[0] : 0.0;
+            const double fN1 = kind == TF_PROBE_INTEGRAL ? end[1] : 0.0;
+            const double val = tf_probe_finish(kind, r, L.N, L.periodic, a.dx[e], f0, fN1, xnode);
+            if (row < a.capacity) a.ring[((int64_t)row * L.nsys + e) * TF_NPROBE + k] = val;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence();
+        if (atomicAdd(&a.cursor[1], 1) == L.nsys - 1) {
+            atomicExch(&a.cursor[1], 0);
+            atomicExch(&a.cursor[0], row < a.capacity ? row + 1 : row);
+        }
+    }
+}
+#endif

@@ -4,21 +4,13 @@
 // case of tf_eval_record (same emitter as tf_eval_F and tf_eval_probe: the per-node values are the bits
 // the reference's lambdified NumPy code computes), a window of nodes start:stop:step and a pool over the
 // nodes of each bin (TF_REC_*, tf_args.h).  The generated record block defines TF_NREC, TF_NREC_HC,
-// TF_REC_USES_X and tf_eval_record before this header is read; every other code object compiles the
-// no-op defaults below (every code object holds every kernel of the table, tf_args.h).
+// TF_REC_USES_X and tf_eval_record before this header is read: it is the tail of a record code object's
+// translation unit and of no other.
 //
 // The walk (on the node window the recorders share with the probes, tf_node.h) and the combine are what the host harness of the test suite (tests/record_host/) also
 // compiles with g++; the kernel itself is at the end of the file.
 #pragma once
 #include "tf_node.h"
-
-#ifndef TF_NREC
-#define TF_NREC 0
-#define TF_NREC_HC 0
-#define TF_REC_USES_X 0
-TF_DEVICE double tf_eval_record(int, const double (&)[TF_NVAR + TF_NH][2 * TF_MP + 1], const double*,
-                                const double*, double, double) { return 0.0; }
-#endif
 
 // b after a.  Maxima / minima as numpy has them (tf_node_extremum: NaN wins; the order of the operands
 // does not matter), the mean's sum is added in the order the caller fixes.
@@ -77,27 +69,25 @@ TF_DEVICE double tf_record_finish(const TfRecordArgs& a, int j, const double* pa
 // memory, as the probes' does: the last workgroup to be done with the row (an integer counter) moves it
 // on, wrapping at the ring's capacity -- a replayed launch writes the next row.  No floating-point atomics.
 extern "C" __global__ void __launch_bounds__(TF_REC_BLOCK) tfk_record(TfRecordArgs a) {
-    if constexpr (TF_NREC > 0) {
-        __shared__ double parts[TF_REC_BLOCK];
-        const int e = blockIdx.x / a.nblk, blk = blockIdx.x - e * a.nblk;
-        const int cpb = TF_REC_BLOCK / a.split;
-        const int row = *(volatile int*)&a.cursor[0];
-        const int c = threadIdx.x / a.split, s = threadIdx.x - c * a.split;
-        const int j = blk * cpb + c;
-        double v = 0.0;
-        if (j < a.ncols && s * a.part < tf_rec_count(a, j)) v = tf_record_part(a, e, j, s);
-        parts[threadIdx.x] = v;
-        __syncthreads();
-        const int jj = blk * cpb + threadIdx.x;
-        if (threadIdx.x < cpb && jj < a.ncols && row >= 0 && row < a.capacity)
-            a.ring[((int64_t)row * a.L.nsys + e) * a.ncols + jj] = tf_record_finish(a, jj, parts + threadIdx.x * a.split);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            __threadfence();
-            if (atomicAdd(&a.cursor[1], 1) == (int)gridDim.x - 1) {
-                atomicExch(&a.cursor[1], 0);
-                atomicExch(&a.cursor[0], row + 1 < a.capacity ? row + 1 : 0);
-            }
+    __shared__ double parts[TF_REC_BLOCK];
+    const int e = blockIdx.x / a.nblk, blk = blockIdx.x - e * a.nblk;
+    const int cpb = TF_REC_BLOCK / a.split;
+    const int row = *(volatile int*)&a.cursor[0];
+    const int c = threadIdx.x / a.split, s = threadIdx.x - c * a.split;
+    const int j = blk * cpb + c;
+    double v = 0.0;
+    if (j < a.ncols && s * a.part < tf_rec_count(a, j)) v = tf_record_part(a, e, j, s);
+    parts[threadIdx.x] = v;
+    __syncthreads();
+    const int jj = blk * cpb + threadIdx.x;
+    if (threadIdx.x < cpb && jj < a.ncols && row >= 0 && row < a.capacity)
+        a.ring[((int64_t)row * a.L.nsys + e) * a.ncols + jj] = tf_record_finish(a, jj, parts + threadIdx.x * a.split);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence();
+        if (atomicAdd(&a.cursor[1], 1) == (int)gridDim.x - 1) {
+            atomicExch(&a.cursor[1], 0);
+            atomicExch(&a.cursor[0], row + 1 < a.capacity ? row + 1 : 0);
         }
     }
 }

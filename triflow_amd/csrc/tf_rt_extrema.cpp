@@ -1,6 +1,6 @@
 // Host runtime of libtriflow_hip: device extrema (tf_extrema_*).  An extrema set is one more code object of
-// the solver's model -- the model's translation unit plus the generated extrema block
-// (codegen.lower_extrema) -- of which only tfk_extrema_count / tfk_extrema_write are launched, on the
+// the solver's model -- the model's generated body, the generated extrema block (codegen.lower_extrema)
+// and tf_extrema.h -- that holds tfk_extrema_count / tfk_extrema_write, launched on the
 // solver's stream, on one of its state slots (tf_observer, tf_solver.h: what the extrema share with the
 // other observers): the two launches per observer that is due, one row [nsys][1 + 4 * max_count] per record.
 //
@@ -56,7 +56,7 @@ int tf_extrema_create(tf_solver* s, const void* code_object, size_t code_size, i
             ex.ring.capacity = (int)std::min(fit, kDefaultRows);
         }
     }
-    p->init(s, code_object, code_size, nconst);
+    p->init(s, code_object, code_size, nconst, TFK_EXTREMA_COUNT, 2);
     p->nblk = (int)tf_solver::cdiv(s->L1.P, 256);
     for (auto& exp : p->obs) {
         Extrema& ex = *exp;

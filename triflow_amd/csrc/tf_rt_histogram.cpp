@@ -1,11 +1,11 @@
 // Host runtime of libtriflow_hip: device histograms (tf_histogram_*).  A histogram set is one more code
-// object of the solver's model -- the model's translation unit plus the generated histogram block
-// (codegen.lower_histograms) -- of which only tfk_hist_partial / tfk_hist_final are launched, on the
+// object of the solver's model -- the model's generated body, the generated histogram block
+// (codegen.lower_histograms) and tf_histogram.h -- that holds tfk_hist_partial / tfk_hist_final, launched on the
 // solver's stream, on one of its state slots (tf_observer, tf_solver.h: what the histograms share with the
 // other observers): the two launches per histogram that is due, one row [nsys][nbins + 3] of counts per
 // record.
 //
-// The two kernels are not in the kernel table (tf_args.h): no other code object holds them.  They are
+// The two kernels are not in the kernel table (tf_args.h).  They are
 // looked up by name in the set's own code object when the handle is created (tfb::kernel_lookup) and
 // launched through what the lookup returned, so they have no launch id, no bit of the timing mask and no
 // line in tf_timing_get: a kernel trace times them.
@@ -66,7 +66,7 @@ int tf_histogram_create(tf_solver* s, const void* code_object, size_t code_size,
         require(h.step >= 1 && h.start >= 0 && h.start <= N && h.stop >= 0 && h.stop <= N,
                 "tf_histogram_create: the window is slice.indices(N) with a step >= 1");
     }
-    p->init(s, code_object, code_size, nconst);
+    p->init(s, code_object, code_size, nconst, 0, 0);
     p->fn_partial = tfb::kernel_lookup(p->module, "tfk_hist_partial");
     p->fn_final = tfb::kernel_lookup(p->module, "tfk_hist_final");
     p->nblk = (int)tf_solver::cdiv(s->L1.P, 256);

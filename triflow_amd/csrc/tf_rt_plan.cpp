@@ -13,6 +13,10 @@
 #include "tf_solver.h"
 
 namespace tfrt { thread_local std::string g_last_error; }
+namespace tfb {
+// (a back end without code objects -- the emulation of the test suite -- links this)
+__attribute__((weak)) void module_resolve(Module*, int, int) {}
+}  // namespace tfb
 
 extern "C" {
 
@@ -45,6 +49,8 @@ int tf_model_create(const tf_model_spec* spec, const void* code, size_t size, tf
     std::unique_ptr<tf_model> m(new tf_model());
     m->spec = *spec;
     m->module = tfb::module_load(code, size);
+    // (the solver's kernels: the ids below the observers' -- an observer's code object holds none of them)
+    tfb::module_resolve(m->module, 0, TFK_PROBE_PARTIAL);
     *out = m.release();
     TF_API_END
 }

@@ -1,7 +1,7 @@
 // Host runtime of libtriflow_hip: device probes (tf_probe_*).  A probe set is a second code object of
-// the solver's model -- the model's translation unit plus the generated probe block (codegen.lower_probes)
-// -- of which only tfk_probe_partial / tfk_probe_final are launched, on the solver's stream, on one of
-// its state slots (tf_observer, tf_solver.h: what the probes share with the recorders).  The rows go into
+// the solver's model -- the model's generated body, the generated probe block (codegen.lower_probes) and
+// tf_probe.h -- that holds tfk_probe_partial / tfk_probe_final, launched on the solver's stream, on one of
+// its state slots (tf_observer, tf_solver.h: what the probes share with the other observers).  The rows go into
 // a ring in device memory; the host waits only when the ring is full (one copy of all of it) and when the
 // caller fetches.
 #include "tf_solver.h"
@@ -41,7 +41,7 @@ int tf_probe_create(tf_solver* s, const void* code_object, size_t code_size, int
     for (int k = 0; k < nprobe; ++k)
         require(kinds[k] >= 0 && kinds[k] < TF_PROBE_KINDS, "tf_probe_create: unknown reduction");
     std::unique_ptr<tf_probe> p(new tf_probe());
-    p->init(s, code_object, code_size, nconst);
+    p->init(s, code_object, code_size, nconst, TFK_PROBE_PARTIAL, 2);
     p->nprobe = nprobe;
     p->capacity = capacity;
     p->nblk = (int)tf_solver::cdiv(s->L1.P, 256);

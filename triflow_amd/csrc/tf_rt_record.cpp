@@ -1,7 +1,7 @@
 // Host runtime of libtriflow_hip: device recorders (tf_record_*).  A recorder set is one more code object
-// of the solver's model -- the model's translation unit plus the generated record block
-// (codegen.lower_records) -- of which only tfk_record is launched, on the solver's stream, on one of its
-// state slots (tf_observer, tf_solver.h: what the recorders share with the probes): one launch per recorder
+// of the solver's model -- the model's generated body, the generated record block (codegen.lower_records)
+// and tf_record.h -- that holds tfk_record, launched on the solver's stream, on one of its state slots
+// (tf_observer, tf_solver.h: what the recorders share with the other observers): one launch per recorder
 // that is due, one row [nsys][ncols] per launch.
 //
 // The rows of a recorder go into a ring of two halves in device memory.  When a half is full, an event on
@@ -110,7 +110,7 @@ int tf_record_create(tf_solver* s, const void* code_object, size_t code_size, in
         r.half = g[5] / 2;
         r.row = (size_t)nsys * r.ncols;
     }
-    p->init(s, code_object, code_size, nconst);
+    p->init(s, code_object, code_size, nconst, TFK_RECORD, 1);
     p->copy = tfb::stream_create();
     for (auto& rp : p->rings) {
         Ring& r = *rp;

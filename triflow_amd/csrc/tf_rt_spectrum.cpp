@@ -1,6 +1,6 @@
 // Host runtime of libtriflow_hip: device spectra (tf_spectrum_*).  A spectrum set is one more code object
-// of the solver's model -- the model's translation unit plus the generated spectrum block
-// (codegen.lower_spectra) -- of which only tfk_spectrum_partial / tfk_spectrum_final are launched, on the
+// of the solver's model -- the model's generated body, the generated spectrum block (codegen.lower_spectra)
+// and tf_spectrum.h -- that holds tfk_spectrum_partial / tfk_spectrum_final, launched on the
 // solver's stream, on one of its state slots (tf_observer, tf_solver.h: what the spectra share with the
 // other observers): the two launches per spectrum that is due, one row [nsys][nmodes] of (re, im) pairs
 // per record.
@@ -42,7 +42,7 @@ int tf_spectrum_create(tf_solver* s, const void* code_object, size_t code_size, 
         require(sp.nmodes >= 1 && sp.nmodes <= TF_SPEC_MAX_MODES, "tf_spectrum_create: 1 ... 64 modes per spectrum");
         require(sp.ring.capacity >= 1, "tf_spectrum_create: a ring has one row at least");
     }
-    p->init(s, code_object, code_size, nconst);
+    p->init(s, code_object, code_size, nconst, TFK_SPECTRUM_PARTIAL, 2);
     p->nblk = (int)tf_solver::cdiv(s->L1.P, 256);
     p->nseg = (int)tf_solver::cdiv(s->L1.M, TF_PROBE_SEG);
     for (auto& spp : p->specs) {

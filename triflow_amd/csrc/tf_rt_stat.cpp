@@ -1,7 +1,7 @@
 // Host runtime of libtriflow_hip: device statistics (tf_stat_*).  A statistic set is one more code object
-// of the solver's model -- the model's translation unit plus the generated statistic block
-// (codegen.lower_statistics) -- of which only tfk_stat is launched, on the solver's stream, on one of its
-// state slots (tf_observer, tf_solver.h: what the statistics share with the probes and the recorders): one
+// of the solver's model -- the model's generated body, the generated statistic block
+// (codegen.lower_statistics) and tf_stat.h -- that holds tfk_stat, launched on the solver's stream, on one
+// of its state slots (tf_observer, tf_solver.h: what the statistics share with the other observers): one
 // launch per statistic that is due.
 //
 // A statistic owns one or two accumulator planes (tf_stat_planes) in the solver's partition-interleaved
@@ -47,7 +47,7 @@ int tf_stat_create(tf_solver* s, const void* code_object, size_t code_size, int3
         require(a.kind >= 0 && a.kind < TF_STAT_KINDS, "tf_stat_create: unknown kind of statistic");
         a.planes = tf_stat_planes(a.kind);
     }
-    p->init(s, code_object, code_size, nconst);
+    p->init(s, code_object, code_size, nconst, TFK_STAT, 1);
     p->nblk = (int)tf_solver::cdiv(s->L1.P, 256);
     p->nseg = (int)tf_solver::cdiv(s->L1.M, TF_PROBE_SEG);
     for (auto& a : p->accs) a->dev.alloc((size_t)a->planes * s->L1.plane, p->bytes);

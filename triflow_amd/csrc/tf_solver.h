@@ -614,10 +614,11 @@ struct tf_solver {
     void check_status(const int* have_flag = nullptr, const double* have_worst = nullptr);
 };
 
-// What the device observers (tf_probe, tf_record, tf_stat, tf_spectrum, tf_extrema, tf_histogram) share.  An observer is one more code object of the solver's
-// model -- the model's translation unit plus a generated block of expressions -- of which only the
-// observer's own kernels are launched, on the solver's stream, on one of its state slots.  Here: the inputs
-// of the node core (TfNodeArgs; csrc/tf_node.h) and the launch.  Rings and copies are the observer's own
+// What the device observers (tf_probe, tf_record, tf_stat, tf_spectrum, tf_extrema, tf_histogram) share.
+// An observer is one more code object of the solver's model -- the model's generated body, a generated
+// block of expressions and the header of the observer's kind -- that holds the kernels of that kind alone;
+// they are launched on the solver's stream, on one of its state slots.  Here: the inputs of the node core
+// (TfNodeArgs; csrc/tf_node.h) and the launch.  Rings and copies are the observer's own
 // (the spectra, the extrema and the histograms: RowRing, below).
 struct tf_observer {
     tf_solver* solver = nullptr;
@@ -628,10 +629,13 @@ struct tf_observer {
     bool own_x = false;                        // the solver holds no x plane (its model does not read x)
     ~tf_observer() { if (module) tfb::module_unload(module); }
 
-    void init(tf_solver* s, const void* code_object, size_t code_size, int nconst) {
+    // first, count: the kind's kernels in the kernel table, which the code object must hold (count 0: none
+    // of the table, the kind finds its kernels by name)
+    void init(tf_solver* s, const void* code_object, size_t code_size, int nconst, int first, int count) {
         solver = s;
         nhc = nconst;
         module = tfb::module_load(code_object, code_size);
+        tfb::module_resolve(module, first, count);
         hc.alloc((size_t)std::max(nconst, 1) * s->nsys, bytes);
         // x of the nodes (argmax / argmin, expressions that read x): the solver's plane when its model
         // reads x (bound with the other inputs, tf_set_x), else a plane of the observer's own (set_x)

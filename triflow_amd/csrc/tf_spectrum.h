@@ -6,22 +6,14 @@
 // per-node values are the bits the reference's lambdified NumPy code computes), and a list of modes m_i in
 // a device buffer.  A row is c[i] = sum_g v_g exp(-2 pi i m_i g / N) over the natural nodes g of a system:
 // np.fft.fft(v)[m_i], unnormalised.  The generated spectrum block defines TF_NSPEC, TF_NSPEC_HC,
-// TF_SPEC_USES_X and tf_eval_spectrum before this header is read; every other code object compiles the
-// no-op defaults below (every code object holds every kernel of the table, tf_args.h).
+// TF_SPEC_USES_X and tf_eval_spectrum before this header is read: it is the tail of a spectrum code object's
+// translation unit and of no other.
 //
 // The twiddle function and the walk of one thread (on the node window the spectra share with the other
 // observers, tf_node.h) are what the host harness of the test suite (tests/spectrum_host/) also compiles
 // with g++; the kernels are at the end of the file.
 #pragma once
 #include "tf_node.h"
-
-#ifndef TF_NSPEC
-#define TF_NSPEC 0
-#define TF_NSPEC_HC 0
-#define TF_SPEC_USES_X 0
-TF_DEVICE double tf_eval_spectrum(int, const double (&)[TF_NVAR + TF_NH][2 * TF_MP + 1], const double*,
-                                  const double*, double, double) { return 0.0; }
-#endif
 
 // exp(-2 pi i r / N) for 0 <= r < N < 2^31: (*re, *im) = (cos, -sin) of 2 pi r / N.  The turn is cut into
 // octants with integers -- q = 8 r / N, rem = 8 r - q N, both exact -- and libm only ever sees
@@ -117,42 +109,40 @@ TF_DEVICE void tf_spectrum_mode(int m, int g0, int N, int n, const double (&v)[T
 // a fixed order; one pair per workgroup, mode and system leaves with plain stores.  Threads without nodes
 // add +0.0.  No atomics on floating-point data: the series are bitwise reproducible.
 extern "C" __global__ void __launch_bounds__(256) tfk_spectrum_partial(TfSpectrumArgs a) {
-    if constexpr (TF_NSPEC > 0) {
-        __shared__ double step[TF_PROBE_SEG][TF_SPEC_MAX_MODES][2];
-        __shared__ double part[4][TF_SPEC_MAX_MODES][2];
-        const int e = blockIdx.x / a.nblk, blk = blockIdx.x - e * a.nblk, sg = blockIdx.y;
-        const int p = blk * 256 + threadIdx.x;
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        const int nm = a.nmodes < TF_SPEC_MAX_MODES ? a.nmodes : TF_SPEC_MAX_MODES;
-        const int N = a.L.N;
-        for (int t = threadIdx.x; t < TF_PROBE_SEG * nm; t += 256) {
-            const int j = t / nm, k = t - j * nm;
-            tf_spec_step(a.modes[k], j, N, &step[j][k][0]);
-        }
-        double v[TF_PROBE_SEG];
-        int n = 0, g0 = 0;
-        if (p < a.L.P) n = tf_spectrum_values(a, e, p, sg, v, &g0);
-        const double poison = tf_spectrum_poison(n, v);
-        __syncthreads();
-        for (int k = 0; k < nm; ++k) {
-            double re = 0.0, im = 0.0;
-            if (n > 0) tf_spectrum_mode(a.modes[k], g0, N, n, v, poison, &step[0][k][0], 2 * TF_SPEC_MAX_MODES, &re, &im);
+    __shared__ double step[TF_PROBE_SEG][TF_SPEC_MAX_MODES][2];
+    __shared__ double part[4][TF_SPEC_MAX_MODES][2];
+    const int e = blockIdx.x / a.nblk, blk = blockIdx.x - e * a.nblk, sg = blockIdx.y;
+    const int p = blk * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nm = a.nmodes < TF_SPEC_MAX_MODES ? a.nmodes : TF_SPEC_MAX_MODES;
+    const int N = a.L.N;
+    for (int t = threadIdx.x; t < TF_PROBE_SEG * nm; t += 256) {
+        const int j = t / nm, k = t - j * nm;
+        tf_spec_step(a.modes[k], j, N, &step[j][k][0]);
+    }
+    double v[TF_PROBE_SEG];
+    int n = 0, g0 = 0;
+    if (p < a.L.P) n = tf_spectrum_values(a, e, p, sg, v, &g0);
+    const double poison = tf_spectrum_poison(n, v);
+    __syncthreads();
+    for (int k = 0; k < nm; ++k) {
+        double re = 0.0, im = 0.0;
+        if (n > 0) tf_spectrum_mode(a.modes[k], g0, N, n, v, poison, &step[0][k][0], 2 * TF_SPEC_MAX_MODES, &re, &im);
 #pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                re = re + __shfl_xor(re, off, 64);
-                im = im + __shfl_xor(im, off, 64);
-            }
-            if (lane == 0) { part[wave][k][0] = re; part[wave][k][1] = im; }
+        for (int off = 32; off > 0; off >>= 1) {
+            re = re + __shfl_xor(re, off, 64);
+            im = im + __shfl_xor(im, off, 64);
         }
-        __syncthreads();
-        if ((int)threadIdx.x < nm) {
-            const int k = threadIdx.x;
-            double re = part[0][k][0], im = part[0][k][1];
-            for (int w = 1; w < 4; ++w) { re = re + part[w][k][0]; im = im + part[w][k][1]; }
-            double* out = a.partial + (((int64_t)e * nm + k) * a.nseg * a.nblk + sg * a.nblk + blk) * 2;
-            out[0] = re;
-            out[1] = im;
-        }
+        if (lane == 0) { part[wave][k][0] = re; part[wave][k][1] = im; }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nm) {
+        const int k = threadIdx.x;
+        double re = part[0][k][0], im = part[0][k][1];
+        for (int w = 1; w < 4; ++w) { re = re + part[w][k][0]; im = im + part[w][k][1]; }
+        double* out = a.partial + (((int64_t)e * nm + k) * a.nseg * a.nblk + sg * a.nblk + blk) * 2;
+        out[0] = re;
+        out[1] = im;
     }
 }
 // grid (nsys), 256 threads: wavefront w reduces modes w, w + 4, ... of one system -- the partials in a
@@ -161,34 +151,32 @@ extern "C" __global__ void __launch_bounds__(256) tfk_spectrum_partial(TfSpectru
 // count of the rows: the launch is queued on the solver's stream between the steps, never inside a
 // captured graph (a replay would write every row where it was captured).
 extern "C" __global__ void __launch_bounds__(256) tfk_spectrum_final(TfSpectrumArgs a) {
-    if constexpr (TF_NSPEC > 0) {
-        const int e = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        const int nb = a.nblk * a.nseg;
-        for (int k = wave; k < a.nmodes; k += 4) {
-            const double* part = a.partial + ((int64_t)e * a.nmodes + k) * nb * 2;
-            double re = 0.0, im = 0.0;
-            for (int b0 = lane; b0 < nb; b0 += 64 * 8) {
-                double vr[8], vi[8];
+    const int e = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nb = a.nblk * a.nseg;
+    for (int k = wave; k < a.nmodes; k += 4) {
+        const double* part = a.partial + ((int64_t)e * a.nmodes + k) * nb * 2;
+        double re = 0.0, im = 0.0;
+        for (int b0 = lane; b0 < nb; b0 += 64 * 8) {
+            double vr[8], vi[8];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int b = b0 + 64 * j;
-                    vr[j] = b < nb ? part[2 * b] : 0.0;
-                    vi[j] = b < nb ? part[2 * b + 1] : 0.0;
-                }
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if (b0 + 64 * j < nb) { re = re + vr[j]; im = im + vi[j]; }
+            for (int j = 0; j < 8; ++j) {
+                const int b = b0 + 64 * j;
+                vr[j] = b < nb ? part[2 * b] : 0.0;
+                vi[j] = b < nb ? part[2 * b + 1] : 0.0;
             }
 #pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                re = re + __shfl_xor(re, off, 64);
-                im = im + __shfl_xor(im, off, 64);
-            }
-            if (lane == 0 && a.row >= 0 && a.row < a.capacity) {
-                double* out = a.ring + (((int64_t)a.row * a.L.nsys + e) * a.nmodes + k) * 2;
-                out[0] = re;
-                out[1] = im;
-            }
+            for (int j = 0; j < 8; ++j)
+                if (b0 + 64 * j < nb) { re = re + vr[j]; im = im + vi[j]; }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            re = re + __shfl_xor(re, off, 64);
+            im = im + __shfl_xor(im, off, 64);
+        }
+        if (lane == 0 && a.row >= 0 && a.row < a.capacity) {
+            double* out = a.ring + (((int64_t)a.row * a.L.nsys + e) * a.nmodes + k) * 2;
+            out[0] = re;
+            out[1] = im;
         }
     }
 }

@@ -5,22 +5,13 @@
 // case of tf_eval_stat (same emitter as tf_eval_F, tf_eval_probe and tf_eval_record: the per-node values
 // are the bits the reference's lambdified NumPy code computes), and a kind (TF_STAT_*, tf_args.h).  The
 // generated statistic block defines TF_NSTAT, TF_NSTAT_HC, TF_STAT_USES_X and tf_eval_stat before this
-// header is read; every other code object compiles the no-op defaults below (every code object holds
-// every kernel of the table, tf_args.h).
+// header is read: it is the tail of a statistic code object's translation unit and of no other.
 //
 // The fold of one sample and the walk of one thread (on the node window the statistics share with the
 // probes and the recorders, tf_node.h) are what the host harness of the test suite (tests/stat_host/)
 // also compiles with g++; the kernel itself is at the end of the file.
 #pragma once
 #include "tf_node.h"
-
-#ifndef TF_NSTAT
-#define TF_NSTAT 0
-#define TF_NSTAT_HC 0
-#define TF_STAT_USES_X 0
-TF_DEVICE double tf_eval_stat(int, const double (&)[TF_NVAR + TF_NH][2 * TF_MP + 1], const double*,
-                              const double*, double, double) { return 0.0; }
-#endif
 
 // Sample k (1, 2, ... as a double) with value v at time t into the accumulators of one node: a0 its
 // element of plane 0, a1 of plane 1 (kinds of two planes only, tf_stat_planes).  Sample 1 is written and
@@ -83,10 +74,8 @@ TF_DEVICE void tf_stat_walk(const TfStatArgs& a, int e, int p, int sg) {
 // host's count of the samples: the launch is queued on the solver's stream between the steps, never
 // inside a captured graph (a replay would fold every sample as the one it was captured with).
 extern "C" __global__ void __launch_bounds__(256) tfk_stat(TfStatArgs a) {
-    if constexpr (TF_NSTAT > 0) {
-        const int e = blockIdx.x / a.nblk, blk = blockIdx.x - e * a.nblk;
-        const int p = blk * 256 + threadIdx.x;
-        if (p < a.L.P) tf_stat_walk(a, e, p, (int)blockIdx.y);
-    }
+    const int e = blockIdx.x / a.nblk, blk = blockIdx.x - e * a.nblk;
+    const int p = blk * 256 + threadIdx.x;
+    if (p < a.L.P) tf_stat_walk(a, e, p, (int)blockIdx.y);
 }
 #endif

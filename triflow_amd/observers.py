@@ -4,9 +4,9 @@
 
 An observer evaluates expressions in the model's own string language at the nodes of a resident state
 slot.  All kinds go through the same node core (``csrc/tf_node.h``): the expressions are discretised with
-the model's stencils (``discretise``), lowered to a block of C that follows the model's translation unit,
-and compiled into one more code object of the model (``compilers.build_observer_code_object``); a handle
-per solver binds it (``_capi.DeviceProbe`` ...) and is fed ``x`` and the host constants of the
+the model's stencils (``discretise``), lowered to a block of C that follows the model's generated body,
+and compiled with the header of their kind into one more code object of the model, which holds that kind's
+kernels alone (``compilers.build_observer_code_object``); a handle per solver binds it (``_capi.DeviceProbe`` ...) and is fed ``x`` and the host constants of the
 expressions.  :class:`ObserverSet` owns that part.
 
 :class:`ItemObserverSet` adds what the sets of named items with a stride share (all kinds but the probes):

@@ -441,6 +441,52 @@ int tf_histogram_fetch(tf_histogram*, int32_t which, double* out, int64_t max_ro
 /* rows of histogram `which` recorded and not fetched yet (no wait) */
 int tf_histogram_pending(tf_histogram*, int32_t which, int64_t* rows);
 
+/* ---- device hooks: a program of statements that WRITES a resident state from model expressions ----
+ * What the reference does with hook(t, fields, pars) on the host -- boundary values tied to other nodes or
+ * fields, an outflow copy, a sponge layer, a positivity clip -- done by two kernels on the state where it
+ * lives.  The contract is the Python function that executes the statements in the order given:
+ *
+ *     for (var, target, expression) in statements:  fields[var][target] = value(expression)
+ *
+ * with the right-hand side evaluated completely before the assignment (NumPy's rule) and every statement
+ * seeing the assignments of the statements before it.  A point statement has a node as its target; the
+ * names of its expression are the fields at that node, and at(name, k) is field `name` at the absolute
+ * node k.  A window statement has the nodes start, start + step, ... < stop; the names are the fields at
+ * the node being assigned (no at(), no stencil: the program assigns in place).  x is the coordinate of the
+ * node, t the time of the call.  A value is the bits NumPy computes from the printed expression
+ * (codegen.lower_hooks: same emitter as F).
+ *
+ * code_object: the model's generated source with the generated hook block and csrc/tf_hook.h, built with
+ * the solver's parameter layout and sweep segment.  It holds tfk_hook_window and tfk_hook_points: they are
+ * not in the kernel table (tf_kernel_name), are resolved by name here and are not covered by
+ * tf_timing_get.  geometry[nstatement][5]: kind (0 point, 1 window), the index of the target variable and
+ * the target (node, 0, 0 or start, stop, step = slice.indices(N), step >= 1; an empty window is legal) --
+ * what the static tables of the block hold, here for the runtime to check against the grid and to size
+ * its launches by: one launch per maximal run of consecutive statements of one kind, a run of window
+ * statements over the chunks and rows the union of its windows touches and no others.
+ *
+ * set_consts: the host constants of the expressions ([nsys][nconst]; powers and libm calls of uniform
+ * arguments, t among them, evaluated by NumPy on the host) for the call before the step and for the call
+ * after it, with the two times.  They live in device memory and nothing of t is a launch argument: upload
+ * them between the steps (never inside one) and a step replayed from a captured graph sees them.
+ * attach: while on, the step functions apply the program wherever they apply the Dirichlet list, after
+ * it -- to the copy of the input with the `before` set, to the result with the `after` set.  idempotent
+ * != 0 says that no right-hand side reads a field, so an input that a step of this solver left with the
+ * same values applied is read in place (as with the Dirichlet list); any other program is applied to a
+ * copy of the input every time.  One program is attached to a solver at a time; attach(0) before the
+ * handle or another program's attach.  apply: one application outside a step with the `before` set, slot
+ * src -> slot dst (src == dst: in place).  A hook belongs to its solver: detach and destroy it first. */
+typedef struct tf_hook tf_hook;
+int tf_hook_create(tf_solver*, const void* code_object, size_t code_size, int32_t nstatement,
+                   const int32_t* geometry, int32_t nconst, tf_hook** out);
+void tf_hook_destroy(tf_hook* hook);
+/* coordinates of the nodes (expressions that read x); ignored when the solver's model reads x itself */
+int tf_hook_set_x(tf_hook*, const double* x /*[nsys][N]*/);
+int tf_hook_set_consts(tf_hook*, const double* before /*[nsys][nconst]*/, const double* after /*[nsys][nconst]*/,
+                       double t_before, double t_after);
+int tf_hook_attach(tf_hook*, int32_t on, int32_t idempotent);
+int tf_hook_apply(tf_hook*, int32_t src, int32_t dst);
+
 #ifdef __cplusplus
 }
 #endif

@@ -152,6 +152,13 @@ SIGNATURES = {
     "tf_histogram_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "tf_histogram_fetch": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int64, c_int64_p]),
     "tf_histogram_pending": (C.c_int, [C.c_void_p, C.c_int32, c_int64_p]),
+    "tf_hook_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, c_int32_p, C.c_int32,
+                                 C.POINTER(C.c_void_p)]),
+    "tf_hook_destroy": (None, [C.c_void_p]),
+    "tf_hook_set_x": (C.c_int, [C.c_void_p, c_double_p]),
+    "tf_hook_set_consts": (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_double, C.c_double]),
+    "tf_hook_attach": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "tf_hook_apply": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
 }
 
 
@@ -785,3 +792,39 @@ class DeviceHistogram(_DeviceRows):
         """Every row of histogram ``which`` recorded since its last fetch, ``[rows][nsys][nbins + 3]``
         int64: the bins, then below, above and NaN (waits for the stream)."""
         return self._fetch_rows(which, self.nbins[which] + 3).astype(np.int64)
+
+
+class DeviceHook(_DeviceObserver):
+    """``tf_hook``: the kernels of one hook program (``hooks.ExpressionHook``) bound to one solver, and the two
+    sets of its host constants.  Unlike the observers it writes the state: attached, the solver's step
+    functions run it where they apply the Dirichlet list."""
+
+    _prefix, _noun = "tf_hook", "hook"
+
+    def __init__(self, solver, code, geometry, nconst):
+        """``geometry``: per statement ``(kind, variable, node, 0, 0)`` or ``(kind, variable, start, stop,
+        step)`` (``codegen.HookStatement.geometry``)."""
+        g = np.ascontiguousarray(geometry, dtype=np.int32).reshape(-1, 5)
+        self.attached = False
+        self._create(solver, code, nconst, len(g), g.ctypes.data_as(c_int32_p), int(nconst))
+
+    def set_consts(self, before, after, t_before, t_after):
+        """``before`` / ``after``: [nsys][nconst] host constants for the call before the step / after it."""
+        self._check_open()
+        b = _f64(before).reshape(self.solver.nsys, self.nconst)
+        a = _f64(after).reshape(self.solver.nsys, self.nconst)
+        self._call("set_consts", _dptr(b) if b.size else None, _dptr(a) if a.size else None,
+                   float(t_before), float(t_after))
+
+    def attach(self, on=True, idempotent=False):
+        self._call("attach", int(bool(on)), int(bool(idempotent)))
+        self.attached = bool(on)
+
+    def apply(self, src, dst):
+        """One application outside a step, with the ``before`` constants: slot ``src`` -> slot ``dst``."""
+        self._call("apply", int(src), int(dst))
+
+    def close(self):
+        if self.handle and self.attached and self.solver.handle:
+            self.attach(False)                      # (the solver's captured steps hold the program's launches)
+        super().close()

@@ -544,16 +544,21 @@ def lower_model(model, parvec_mask=0, seg=8, sweep_block=64):
 PROBE_REDUCTIONS = ("sum", "mean", "integral", "max", "min", "argmax", "argmin")
 
 
-def _lower_node_expressions(model, exprs, parvec_mask):
+def _lower_node_expressions(model, exprs, parvec_mask, extra_names=None, extra_uniform=(), extra_args=()):
     """What the probes and the recorders share: discretised SymPy expressions over the model's symbolic
     arguments, printed by the same lambdify call as F and emitted by the same ``_CEmitter``.  Returns
     the lines that open the per-node body (the window / parameter names, the hoisted divisors), the C
     expressions, the uniform powers / libm calls evaluated on the host, whether ``x`` is read, the
-    model's parameter names and its mode of Heaviside / DiracDelta / Piecewise."""
+    model's parameter names and its mode of Heaviside / DiracDelta / Piecewise.  ``extra_names``: further
+    printed names and their C expressions (``extra_uniform``: those that are the same at every node;
+    ``extra_args``: their symbols, which follow the model's own in the lambdify call) -- the hooks' ``t``
+    and ``at()`` reads."""
     fields = list(model._dep_vars) + list(model._help_funcs)
     pars = list(model._pars)
     mp = max((model._window_range - 1) // 2, 1)
     names, decls, uniform = _stencil_names(fields, pars, mp, parvec_mask)
+    names.update(extra_names or {})
+    uniform |= set(extra_uniform)
     import sympy
     mode = heaviside_mode(model)
     for e in exprs:
@@ -565,7 +570,7 @@ def _lower_node_expressions(model, exprs, parvec_mask):
             raise UnsupportedExpression("function 'Heaviside' is not supported in a probe or recorder: the HIP "
                                         "compiler takes it as identically one, as the reference does in J; "
                                         "write the step with Max / Min / sign" + _EXACT_HINT)
-    nodes = _printed_expressions(model._symbolic_args, list(exprs), mode)
+    nodes = _printed_expressions([*model._symbolic_args, *extra_args], list(exprs), mode)
     first = _CEmitter(names, uniform, mode)         # pass 1: count divisor reuse
     for n in nodes:
         first.visit(n)
@@ -691,6 +696,108 @@ def lower_histograms(model, exprs, parvec_mask=0):
     return _lower_switch(model, exprs, parvec_mask, "HIST", "tf_eval_hist", "nhist", "device histograms", "lower_histograms")
 
 
+#: kinds of a hook statement, in the order of TF_HOOK_POINT / TF_HOOK_WINDOW of csrc/tf_args.h
+HOOK_KINDS = ("point", "window")
+
+
+class HookStatement:
+    """One statement ``fields[var][target] = expr`` of a hook program, laid out for a grid: ``kind`` of
+    ``HOOK_KINDS``; ``var`` the index of the dependent variable; ``target`` the node ``0 ... N - 1`` (point)
+    or ``(start, stop, step)`` = ``slice.indices(N)`` (window); ``expr`` a SymPy expression over the centre
+    symbols of the model's fields, its parameters, ``x``, ``dx``, ``t`` and the symbols of ``at``;
+    ``at``: ``(symbol, field index, node 0 ... N - 1)`` per ``at()`` read (point statements only)."""
+
+    def __init__(self, kind, var, target, expr, at=()):
+        self.kind, self.var, self.target, self.expr, self.at = kind, int(var), target, expr, tuple(at)
+
+    @property
+    def geometry(self):
+        """``(kind, var, a, b, c)``: a point's node, 0, 0; a window's start, stop, step."""
+        a, b, c = (self.target, 0, 0) if self.kind == "point" else self.target
+        return (HOOK_KINDS.index(self.kind), self.var, int(a), int(b), int(c))
+
+
+def hook_runs(statements):
+    """``[(first, count)]``: the maximal runs of consecutive statements of one kind -- a launch each."""
+    runs = []
+    for k, st in enumerate(statements):
+        if runs and statements[runs[-1][0]].kind == st.kind:
+            runs[-1][1] += 1
+        else:
+            runs.append([k, 1])
+    return [tuple(r) for r in runs]
+
+
+def lower_hooks(model, statements, parvec_mask=0):
+    """A hook program (``hooks.ExpressionHook``: :class:`HookStatement` in execution order) -> ``(block,
+    spec)``: the C block that follows the model's own translation unit (``TF_NHOOK`` ... ``tf_eval_hook``,
+    statement ``k`` being case ``k``, and the static tables of the statements: kind, target variable,
+    target, ``at()`` reads as (field, node) pairs gathered per statement -- read by csrc/tf_hook.h) and the
+    constants the runtime needs.  Lowered as the observers are (``_lower_node_expressions``): a value is the
+    bits NumPy computes from the printed expression.  ``t`` is one more uniform name: a power or libm call
+    of uniform arguments that reads it is a host constant, evaluated per call (``eval_host_constants(...,
+    t=t)``), and a bare ``t`` is the host constant ``"t"`` itself, so nothing of ``t`` is a launch argument.
+    ``spec["geometry"]`` is what ``tf_hook_create`` takes, ``spec["runs"]`` the launches of one application."""
+    import sympy
+    statements = list(statements)
+    if not statements:
+        raise ValueError("a hook program has one statement at least")
+    maxat = max([len(st.at) for st in statements] + [1])
+    at_syms = [sympy.Symbol("tf_at_%d" % j) for j in range(maxat)]
+    exprs = []
+    for st in statements:
+        if st.kind not in HOOK_KINDS:
+            raise ValueError("hook statement of unknown kind %r" % (st.kind,))
+        if st.kind == "window" and st.at:
+            raise UnsupportedExpression("at() in a window statement")
+        exprs.append(sympy.sympify(st.expr).xreplace({sym: at_syms[j] for j, (sym, _, _) in enumerate(st.at)}))
+    extra = {"t": "tf_t", **{"tf_at_%d" % j: "tf_at[%d]" % j for j in range(maxat)}}
+    lines, out, hc_list, uses_x, pars, mode = _lower_node_expressions(
+        model, exprs, parvec_mask, extra_names=extra, extra_uniform=("t",),
+        extra_args=[sympy.Symbol("t"), *at_syms])
+    if any("tf_t" in _tokens(text) for text in out + lines):
+        # (a bare t: the last host constant, so it comes with the others and from the same buffer)
+        hc_list = hc_list + ["t"]
+        lines.insert(0, "    const double tf_t = tf_hc[%d];" % (len(hc_list) - 1))
+    lines += ["    (void)tf_at;", "    switch (k) {"]
+    lines += ["    case %d: return %s;" % (i, c) for i, c in enumerate(out)]
+    lines += ["    default: return 0.0;", "    }"]
+    geometry = [st.geometry for st in statements]
+    at_first, at_field, at_node = [], [], []
+    for st in statements:
+        at_first.append(len(at_field))
+        at_field += [int(f) for _, f, _ in st.at]
+        at_node += [int(g) for _, _, g in st.at]
+
+    def arr(name, values):
+        return "static constexpr int %s[%d] = {%s};" % (name, max(len(values), 1),
+                                                        ", ".join(str(int(v)) for v in values) or "0")
+    n = len(statements)
+    block = "\n".join([
+        "// device hooks, generated by triflow_amd.codegen.lower_hooks -- do not edit",
+        *("// %s %d: %s[%s] = %s" % (st.kind, k, st.var, st.target, e)
+          for k, (st, e) in enumerate(zip(statements, exprs))),
+        "#define TF_NHOOK %d" % n,
+        "#define TF_NHOOK_HC %d" % len(hc_list),
+        "#define TF_HOOK_USES_X %d" % (1 if uses_x else 0),
+        "#define TF_HOOK_MAXAT %d" % maxat,
+        "// per statement: kind (0 point, 1 window), target variable, target (node, 0, 0 / start, stop, step)",
+        arr("tf_hook_kind", [g[0] for g in geometry]), arr("tf_hook_var", [g[1] for g in geometry]),
+        arr("tf_hook_a", [g[2] for g in geometry]), arr("tf_hook_b", [g[3] for g in geometry]),
+        arr("tf_hook_c", [g[4] for g in geometry]),
+        "// the at() reads of a statement: tf_hook_nat of them from tf_hook_at0 on, (field, node) pairs",
+        arr("tf_hook_nat", [len(st.at) for st in statements]), arr("tf_hook_at0", at_first),
+        arr("tf_hook_at_field", at_field), arr("tf_hook_at_node", at_node),
+        "TF_DEVICE double tf_eval_hook(int k, const double (&w)[TF_NVAR + TF_NH][2 * TF_MP + 1], "
+        "const double* par, const double* tf_hc, double dx, double xc, const double* tf_at) {",
+        "\n".join(lines),
+        "}",
+        ""])
+    spec = dict(nhook=n, host_consts=hc_list, pars=pars, uses_x=int(uses_x), heaviside=mode,
+                geometry=geometry, runs=hook_runs(statements), maxat=maxat)
+    return block, spec
+
+
 def _proportional_entries(model, j_uniform, heaviside="one"):
     """Jacobian entries that are an exact power-of-two multiple of an earlier node-dependent
     entry (``-q*dxT/h`` differentiated with respect to ``T_m1`` and ``T_p1``; ``We*h*dxxxh`` with
@@ -765,11 +872,14 @@ _HOST_NS_MODE = {
 }
 
 
-def eval_host_constants(spec, dx, par_values):
+def eval_host_constants(spec, dx, par_values, t=None):
     """Values of the model's uniform power / libm sub-expressions for one system,
-    computed exactly as the reference's lambdified NumPy code computes them."""
+    computed exactly as the reference's lambdified NumPy code computes them.  ``t``: the time a hook is
+    called with (the host constants of a hook program may read it)."""
     env = {name: np.float64(np.ravel(v)[0]) for name, v in zip(spec["pars"], par_values)}
     env["dx"] = np.float64(dx)
+    if t is not None:
+        env["t"] = np.float64(t)
     out = []
     for src_ in spec["host_consts"]:
         with np.errstate(all="ignore"):

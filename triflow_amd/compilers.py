@@ -65,14 +65,14 @@ def extra_flags(*flags):
 #: translation units of the host runtime (see the header of csrc/tf_solver.h)
 RUNTIME_SOURCES = ("tf_rt_plan.cpp", "tf_rt_io.cpp", "tf_rt_steps.cpp", "tf_rt_diag.cpp",
                    "tf_solver_sweeps.cpp", "tf_solver_linear.cpp", "tf_rt_probe.cpp", "tf_rt_record.cpp",
-                   "tf_rt_stat.cpp", "tf_rt_spectrum.cpp", "tf_rt_extrema.cpp", "tf_rt_histogram.cpp")
+                   "tf_rt_stat.cpp", "tf_rt_spectrum.cpp", "tf_rt_extrema.cpp", "tf_rt_histogram.cpp", "tf_rt_hook.cpp")
 #: the headers a model's own code object is compiled from ...
 _SKELETON = ("tf_args.h", "tf_math.h", "tf_layout.h", "tf_kernels.h", "tf_crs.h", "tf_coop_hip.h", "tf_cr2_hip.h",
              "tf_cr3_hip.h", "tf_cr_io.h", "tf_entry_hip.h")
 #: ... and an observer's, by kind: the layout, the node core and the kind's own header, which ends its unit
 _OBSERVER_SKELETON = {kind: ("tf_args.h", "tf_math.h", "tf_layout.h", "tf_node.h", header) for kind, header in (
     ("probe", "tf_probe.h"), ("record", "tf_record.h"), ("stat", "tf_stat.h"), ("spectrum", "tf_spectrum.h"),
-    ("extrema", "tf_extrema.h"), ("histogram", "tf_histogram.h"))}
+    ("extrema", "tf_extrema.h"), ("histogram", "tf_histogram.h"), ("hook", "tf_hook.h"))}
 _TU_HEAD = ('#include <hip/hip_runtime.h>\n'
             '#define TF_DEVICE __device__ __forceinline__\n'
             '%s'

@@ -514,8 +514,31 @@ struct TfHistArgs : TfNodeArgs {
     unsigned* partial;             // [nsys][nseg * nblk][nbins + 3]
     double* ring;                  // [capacity][nsys][nbins + 3]
 };
+// Device hooks (tf_hook.h, tf_rt_hook.cpp): a program of statements fields[var][target] = expression that
+// WRITES a resident state, executed in the order given; every statement sees the assignments of the ones
+// before it.  A point statement assigns one node (and may read other nodes through at()), a window
+// statement the nodes start, start + step, ... < stop with the expression at the node being assigned.
+// Kinds, targets and at() reads are static tables of the generated block (codegen.lower_hooks); a launch
+// takes one maximal run of consecutive statements of one kind: first ... first + count - 1.
+//   tfk_hook_window: grid (nsys * nblk, nsg), 256 threads: thread x of workgroup blk walks the rows of
+//     segment sg0 + blockIdx.y (TF_PROBE_SEG rows) of chunk p0 + blk * 256 + x, of the chunks p0 ... p1 - 1:
+//     the chunks and rows the union of the run's windows touches.
+//   tfk_hook_points: grid (ceil(nsys / 64)), 64 threads, one thread per system.
+// `hc` of the base is the set of host constants of this application (the call before the step or the one
+// after it): t reaches the kernels through it and through nothing else, so a captured launch replays with
+// the t uploaded last.  These two kernels are not in the kernel table below: the runtime resolves them by
+// name (tfb::kernel_lookup) in a code object of kind "hook".
+#define TF_HOOK_POINT 0
+#define TF_HOOK_WINDOW 1
+struct TfHookArgs : TfNodeArgs {
+    double* out;                   // [nvar] planes: the planes of `fields` (the program assigns in place)
+    int first, count;              // the run: statements first ... first + count - 1
+    int p0, p1;                    // window runs: the chunks p0 ... p1 - 1 of every system ...
+    int sg0, nblk;                 // ... from segment sg0 on; workgroups per system and segment row
+};
 // (passed by value to kernels of code objects the host did not compile: the bytes are the contract)
 // (the base comes first and the members follow in their order: the sizes pin the bytes)
+static_assert(sizeof(TfHookArgs) == 128, "TfHookArgs changed its layout");
 static_assert(sizeof(TfHistArgs) == 160, "TfHistArgs changed its layout");
 static_assert(sizeof(TfNodeArgs) == 96, "TfNodeArgs changed its layout");
 static_assert(sizeof(TfProbeArgs) == 144, "TfProbeArgs changed its layout");

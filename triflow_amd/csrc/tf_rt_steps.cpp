@@ -80,7 +80,7 @@ void step_erk(tf_solver* s, int32_t src, int32_t dst, double dt, int32_t ns, con
     // The hooked copy of the input goes to a work buffer, not into dst as in the implicit steps: the fused
     // last stage reads the window of its input while it writes dst.
     const double* Uin = s->st(src);
-    if (s->ndir > 0 && !s->input_is_hooked(src)) {
+    if (s->has_hook() && !s->input_is_hooked(src)) {
         s->copy(s->Wstage.p, Uin, (size_t)s->vecn() * sizeof(double));
         s->apply_dirichlet(s->Wstage.p);
         Uin = s->Wstage.p;
@@ -163,7 +163,7 @@ int tf_step_theta(tf_solver* s, int32_t src, int32_t dst, double dt, double thet
     TF_API_BEGIN
     require(s, "null solver");
     const std::string key = "T|" + std::to_string(src) + ">" + std::to_string(dst) + "|" + bits_of(dt) + "|" +
-        bits_of(theta) + "|" + std::to_string(s->ndir) + (s->input_is_hooked(src) ? "h" : "c") + "|" + std::to_string(s->sweeps_for(theta * dt)) + "|" + std::to_string(s->refine) +
+        bits_of(theta) + "|" + s->hook_key(src) + "|" + std::to_string(s->sweeps_for(theta * dt)) + "|" + std::to_string(s->refine) +
         s->slot_key(theta * dt);      // (a step that reuses a factorisation is another string of launches, on its buffers)
     s->prepare_step(theta * dt);
     s->run_graphed(key, s->step_graphable(theta * dt), [&] { step_theta(s, src, dst, dt, theta); });
@@ -178,7 +178,7 @@ int tf_step_row(tf_solver* s, int32_t src, int32_t dst, double dt, int32_t ns,
     require(s && alpha && gamma && b, "null argument");
     require(ns >= 1 && ns <= 6, "tf_step_row: 1 <= s <= 6");
     std::string key = "R|" + std::to_string(src) + ">" + std::to_string(dst) + "|" + bits_of(dt) + "|" +
-        std::to_string(ns) + "|" + std::to_string(hook_after) + "|" + std::to_string(s->ndir) + (s->input_is_hooked(src) ? "h" : "c") + "|" +
+        std::to_string(ns) + "|" + std::to_string(hook_after) + "|" + s->hook_key(src) + "|" +
         std::to_string(s->sweeps_for(gamma[0] * dt)) + "|" + std::to_string(s->refine) + "|" + (b_pred && err_out ? "e" : "-") +
         s->slot_key(gamma[0] * dt);
     s->prepare_step(gamma[0] * dt);
@@ -214,8 +214,7 @@ int tf_step_erk(tf_solver* s, int32_t src, int32_t dst, double dt, int32_t ns, c
     require(!(d && err_out) || any_d, "tf_step_erk: every weight d_i of the estimate is zero");
     // (the step is a linear chain of launches with nothing for the host to decide: always graphable)
     std::string key = "E|" + std::to_string(src) + ">" + std::to_string(dst) + "|" + bits_of(dt) + "|" +
-        std::to_string(ns) + "|" + std::to_string(hook_after) + "|" + std::to_string(s->ndir) +
-        (s->input_is_hooked(src) ? "h" : "c") + "|" + (d && err_out ? "e" : "-") + (s->erk_fused ? "F" : "U");
+        std::to_string(ns) + "|" + std::to_string(hook_after) + "|" + s->hook_key(src) + "|" + (d && err_out ? "e" : "-") + (s->erk_fused ? "F" : "U");
     for (int i = 0; i < ns * ns; ++i) key += bits_of(a[i]) + ",";
     for (int i = 0; i < ns; ++i) key += bits_of(b[i]) + "," + (d ? bits_of(d[i]) : std::string("-")) + ",";
     s->erk_prepare(ns);
@@ -337,7 +336,7 @@ void step_bdf2(tf_solver* s, int32_t src, int32_t dst, double dt, tf_solver::Bdf
     double* U = s->st(dst);
     s->slot_written(dst);
     const double* Uin;
-    if (!h && s->ndir > 0 && !s->input_is_hooked(src)) {
+    if (!h && s->has_hook() && !s->input_is_hooked(src)) {
         // The history of the next step is this step's *hooked* input (the oracle keeps the hooked
         // copy, oracle/numpy_path.py BDF2._prev), and with the history in a state slot that slot is
         // src itself: the boundary values go into src in place (no copy into dst) and the slot is

@@ -14,6 +14,7 @@
 //   tf_rt_spectrum.cpp     device spectra (tf_spectrum_*) }
 //   tf_rt_extrema.cpp      device extrema (tf_extrema_*)  }
 //   tf_rt_histogram.cpp    device histograms (tf_histogram_*) }
+//   tf_rt_hook.cpp         device hooks (tf_hook_*): programs that write a state, run where the Dirichlet list is
 #pragma once
 #include "../../include/triflow_hip.h"
 #include "tf_args.h"
@@ -225,6 +226,25 @@ struct tf_solver {
     int ndir = 0;
     int *dir_var = nullptr, *dir_node = nullptr;
     DevBuf dir_val, dir_val_post;   // values applied before the step (hook at t) / after (t+dt)
+    // The attached hook program (tf_hook_attach, tf_rt_hook.cpp; none: nullptr).  apply_dirichlet runs it
+    // after the Dirichlet list through prog_apply, with the `before` set of its constants or the `after`
+    // one.  prog_idem: no right-hand side reads a field, so a slot that holds its values already is read in
+    // place (input_is_hooked); any other program is applied to a copy of the input every time.  prog_sig /
+    // prog_sig_post: what identifies the values an idempotent program writes before / after a step -- the
+    // program, the upload count of the parameters and the two sets of constants.
+    void* prog = nullptr;
+    void (*prog_apply)(void* prog, double* fields, bool post) = nullptr;
+    bool prog_idem = false;
+    uint64_t prog_uid = 0;
+    std::vector<double> prog_sig, prog_sig_post;
+    bool has_hook() const { return ndir > 0 || prog != nullptr; }
+    // the part of a captured step's key that names the hooks: the Dirichlet list, whether the input is
+    // copied, the attached program and its kind
+    std::string hook_key(int src) const {
+        std::string k = std::to_string(ndir) + (input_is_hooked(src) ? "h" : "c");
+        if (prog) k += "P" + std::to_string(prog_uid) + (prog_idem ? "i" : "n");
+        return k;
+    }
 
     DevBuf stamp_buf;              // diagnostic builds: 64 stamps per solver level (tf_debug_stamps)
     int* csc_map = nullptr;        // tf_set_csc_map: value-table index of every CSC data slot
@@ -499,6 +519,9 @@ struct tf_solver {
     bool hook_in_place = true;                     // (TRIFLOW_HOOK_IN_PLACE=0: A/B runs, tests)
     void slot_written(int slot) { if (slot >= 0 && (size_t)slot < slot_hook.size()) slot_hook[slot].clear(); }
     void mark_hooked(int slot, bool post = true);
+    // what a slot's contents satisfy after the hooks were applied: the Dirichlet values, then the signature
+    // of the attached program (without one: the Dirichlet values alone, as ever)
+    std::vector<double> hook_sig(bool post) const;
     bool input_is_hooked(int src) const;
     const double* stage_input(int src, double* U);
 

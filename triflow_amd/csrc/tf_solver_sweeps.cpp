@@ -1,4 +1,4 @@
-// tf_solver: elementary steps -- stencil sweeps, J @ v, vector algebra, declarative hooks (see tf_solver.h)
+// tf_solver: elementary steps -- stencil sweeps, J @ v, vector algebra, hooks (see tf_solver.h)
 #include "tf_solver.h"
 
 void tf_solver::vec(int op, double* out, const double* base, int nterms, const double* const* xs, const double* cs, int64_t n, int red_slot, const double* cs2) {
@@ -50,11 +50,13 @@ void tf_solver::download_aos(const double* planes, double* host, int ncomp) {
 }
 
 void tf_solver::apply_dirichlet(double* fields, bool post) {
-    if (ndir == 0) return;
-    TfDirichletArgs a;
-    a.L = L1; a.fields = fields; a.n = ndir; a.var = dir_var; a.node = dir_node;
-    a.value = post ? dir_val_post.p : dir_val.p;
-    launch(TFK_DIRICHLET, cdiv((int64_t)ndir * nsys, 64), 1, 64, &a, sizeof(a));
+    if (ndir > 0) {
+        TfDirichletArgs a;
+        a.L = L1; a.fields = fields; a.n = ndir; a.var = dir_var; a.node = dir_node;
+        a.value = post ? dir_val_post.p : dir_val.p;
+        launch(TFK_DIRICHLET, cdiv((int64_t)ndir * nsys, 64), 1, 64, &a, sizeof(a));
+    }
+    if (prog) prog_apply(prog, fields, post);          // the attached hook program (tf_rt_hook.cpp)
 }
 
 void tf_solver::sweep(const double* fields, bool with_j, int nterms, const double* const* kx, const double* kc, double fscale, double* Fout) {
@@ -244,16 +246,26 @@ void tf_solver::spmv_stage(int nterms, const double* const* vx, const double* vc
 void tf_solver::mark_hooked(int slot, bool post) {
     if (slot < 0) return;
     if ((size_t)slot >= slot_hook.size()) slot_hook.resize((size_t)slot + 1);
-    slot_hook[slot] = post ? dir_post_h : dir_h;
+    slot_hook[slot] = hook_sig(post);
+}
+
+std::vector<double> tf_solver::hook_sig(bool post) const {
+    std::vector<double> sig = post ? dir_post_h : dir_h;
+    if (prog) {
+        const std::vector<double>& p = post ? prog_sig_post : prog_sig;
+        sig.insert(sig.end(), p.begin(), p.end());
+        sig.push_back((double)par_ver);                // (the program reads the parameters themselves)
+    }
+    return sig;
 }
 
 bool tf_solver::input_is_hooked(int src) const {
-    return hook_in_place && ndir > 0 && src >= 0 && (size_t)src < slot_hook.size() &&
-           !slot_hook[src].empty() && slot_hook[src] == dir_h;
+    if (!hook_in_place || !has_hook() || (prog && !prog_idem)) return false;
+    return src >= 0 && (size_t)src < slot_hook.size() && !slot_hook[src].empty() && slot_hook[src] == hook_sig(false);
 }
 
 const double* tf_solver::stage_input(int src, double* U) {
-    if (ndir == 0 || input_is_hooked(src)) return st(src);
+    if (!has_hook() || input_is_hooked(src)) return st(src);
     copy(U, st(src), (size_t)vecn() * sizeof(double));
     apply_dirichlet(U);
     return U;

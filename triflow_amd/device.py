@@ -12,6 +12,9 @@ uploaded.  Containers returned by a step are *device backed*
 * ``null_hook``                      nothing to do;
 * a :class:`DirichletHook`           applied by a kernel at the places the
                                      reference calls ``hook`` (no host traffic);
+* an :class:`ExpressionHook`         a program of statements in the model's language
+                                     (``hooks.py``), run by two kernels at the same
+                                     places (no host traffic);
 * any other callable                 the generic, slow path: the fields are
                                      brought to the host, the callable runs
                                      there, the result is uploaded again.
@@ -20,6 +23,9 @@ uploaded.  Containers returned by a step are *device backed*
 import weakref
 
 import numpy as np
+
+from . import codegen
+from .hooks import ExpressionHook
 
 
 def null_hook(t, fields, pars):
@@ -111,6 +117,9 @@ class Stepper:
         self._bound_pars = None
         self._bound_x = None
         self._dirichlet = None
+        self._programs = weakref.WeakKeyDictionary()    # ExpressionHook -> _Program (one tf_hook handle each)
+        self._attached = None                           # the _Program the step functions run, if any
+        self._inputs = None                             # (x, parameter values) of the last bind
         self._queued_owner = {}       # estimate mailbox -> (token of the step queued into it last, its scheme)
 
     # ---- slots ------------------------------------------------------------------
@@ -224,6 +233,7 @@ class Stepper:
         cm = self.compiled
         x = np.asarray(fields["x"])
         values = [pars[k] for k in cm.pars]        # KeyError for a missing parameter
+        self._inputs = (x, values)
         pkey, xkey = self._input_keys(x, values)
         helper_free = cm.nh == 0
         if helper_free and pkey is not None and pkey == self._bound_pars and xkey == self._bound_x:
@@ -234,11 +244,21 @@ class Stepper:
 
     def set_hook(self, hook, t=0.0, t_after=None):
         """Boundary values the step kernels apply before (``t``) and after
-        (``t_after``) the step."""
+        (``t_after``) the step, or the program they run there (an :class:`ExpressionHook`: after
+        ``bind``, whose ``x`` and parameters its host constants are computed from)."""
+        program = self.program(hook) if isinstance(hook, ExpressionHook) else None
+        if self._attached is not None and self._attached is not program:
+            self._attached.handle.attach(False)
+            self._attached = None
         if not isinstance(hook, DirichletHook):
             if self._dirichlet:
                 self.solver.set_dirichlet(())
                 self._dirichlet = ()
+            if program is not None:
+                program.update(t, t if t_after is None else t_after, self._inputs[0], [self._inputs[1]])
+                if self._attached is None:
+                    program.handle.attach(True, hook.idempotent)
+                    self._attached = program
             return
         layout = hook.layout(self.compiled.model._dep_vars)
         before = hook.values_at(t)
@@ -251,6 +271,67 @@ class Stepper:
         if layout:
             self.solver.set_dirichlet_values(before, after)
         self._dirichlet = key
+
+
+    def program(self, hook):
+        """The binding of an :class:`ExpressionHook` to this stepper's solver: one ``tf_hook`` handle per
+        stepper and program, made on first use."""
+        if hook.model is not self.compiled.model:
+            raise ValueError("this ExpressionHook was built for another model object")
+        prog = self._programs.get(hook)
+        if prog is None:
+            prog = self._programs[hook] = _Program(hook, self.compiled.model, self.solver)
+        return prog
+
+    def apply_hook(self, hook, t, fields, pars):
+        """One application of an :class:`ExpressionHook` at ``t`` outside a step (where ``Simulation`` calls
+        the hook before the scheme): the state of ``fields`` goes through the program into a free slot and
+        comes back as a new device-backed container; nothing touches the host."""
+        self.bind(fields, pars)
+        self.set_hook(hook, t, t)
+        src = self.acquire(fields)
+        dst = self.free_slot(exclude=(src,))
+        self._attached.handle.apply(src, dst)
+        return self.wrap(fields, dst)
+
+
+class _Program:
+    """An :class:`ExpressionHook` on one solver: its code object (``codegen.lower_hooks`` for the solver's
+    grid and parameter layout), the ``tf_hook`` handle and what was last uploaded to it."""
+
+    def __init__(self, hook, model, solver):
+        from . import compilers
+        from ._capi import DeviceHook
+        spec = solver.model.spec
+        block, self.spec = hook.lowered(solver.N, spec["parvec_mask"])
+        hsaco = compilers.build_observer_code_object(model, block, "hook", spec["parvec_mask"], spec["seg"],
+                                                     spec["sweep_block"])
+        with open(hsaco, "rb") as f:
+            code = f.read()
+        self.solver = solver
+        self.handle = DeviceHook(solver, code, self.spec["geometry"], len(self.spec["host_consts"]))
+        self._xkey = self._ckey = None
+
+    def update(self, t, t_after, x, member_pars):
+        """The inputs for a step from ``t`` to ``t_after``: ``x`` (``[N]`` or ``[nsys][N]``) and the host
+        constants of the expressions for the two calls, computed per system from ``member_pars`` (per
+        system, the model's parameter values) -- uploaded when they changed."""
+        solver = self.solver
+        x = np.asarray(x, dtype=float)
+        xkey = (x.shape, float(x.flat[0]), float(x.flat[-1]))
+        x2 = np.broadcast_to(x, (solver.nsys, solver.N))
+        if xkey != self._xkey:
+            if not solver.model.spec["uses_x"]:          # (else the kernels read the solver's own x plane)
+                self.handle.set_x(x2)
+            self._xkey = xkey
+        dxs = (x2[:, -1] - x2[:, 0]) / (solver.N - 1)
+        sets = [np.array([codegen.eval_host_constants(self.spec, dxs[e], member_pars[e], t=when)
+                          for e in range(solver.nsys)], dtype=float).reshape(solver.nsys, -1)
+                for when in (t, t_after)]
+        ckey = (sets[0].tobytes(), sets[1].tobytes())    # (whatever of t a statement reads is one of them)
+        if ckey != self._ckey:
+            self.handle.set_consts(sets[0], sets[1], t, t_after)
+            self._ckey = ckey
 
 
 def _backing_of(fields):

@@ -94,9 +94,28 @@ class Ensemble(Observed):
         self._keep = s.nstate - 1 if s.nstate >= 3 else None
         if self._keep is not None:
             s.copy_state(0, self._keep)
-        if hook is not None:
-            s.set_dirichlet(hook.entries(dep, 0.0))
         self.scheme, self.theta = scheme, theta
+        self._program = None
+        self._x = x
+        self._member_pars = [[np.asarray(v)[e] if np.ndim(v) >= 1 and np.shape(v)[0] == self.nsys else v
+                              for v in values] for e in range(self.nsys)]
+        from .device import ExpressionHook, _Program
+        if isinstance(hook, ExpressionHook):
+            # a program of statements (hooks.py): applied to every member with that member's parameters
+            # and the ensemble's t, where the step functions apply the Dirichlet list
+            if hook.model is not model:
+                raise ValueError("this ExpressionHook was built for another model object")
+            if hook.parameters is not None:
+                raise ValueError("an Ensemble binds its parameters once: an ExpressionHook with a "
+                                 "parameters= callable is not supported here")
+            if scheme == "BDF2" and not hook.idempotent:
+                raise ValueError("BDF2 hooks its input in place: only an idempotent ExpressionHook (no "
+                                 "right-hand side reads a field) can be attached to it")
+            self._program = _Program(hook, model, s)
+            self._program.update(0.0, 0.0, x, self._member_pars)
+            self._program.handle.attach(True, hook.idempotent)
+        elif hook is not None:
+            s.set_dirichlet(hook.entries(dep, 0.0))
         self.tab = TABLEAUX.get(scheme)
         # "SSPRK3" / "RK4": fixed explicit steps (tf_step_erk)
         self.erk = ERK_TABLEAUX[scheme] if scheme in ("SSPRK3", "RK4") else None
@@ -105,16 +124,16 @@ class Ensemble(Observed):
         # started from -- the step reads it there and the history is never copied (tf_step_bdf2_from)
         self._nrot = s.nstate if self._keep is None else self._keep
         self._bdf_prev, self._bdf_dt = -1, None
-        # device probes: coordinates and per-member parameter values their host constants need
-        self._x = x
-        self._member_pars = [[np.asarray(v)[e] if np.ndim(v) >= 1 and np.shape(v)[0] == self.nsys else v
-                              for v in values] for e in range(self.nsys)]
+        # (device probes and hooks: self._x, self._member_pars -- the coordinates and per-member parameter
+        # values their host constants need)
         self._nsteps = 0
 
     def step(self, dt):
         """One fixed step of every member (asynchronous: returns after the launches)."""
         s, src = self.solver, self.cur
         dst = (src + 1) % (s.nstate if self._keep is None else self._keep)
+        if self._program is not None:       # the hook's constants at t and t + dt (uploaded when they changed)
+            self._program.update(self.t, self.t + dt, self._x, self._member_pars)
         if self.scheme == "Theta":
             s.step_theta(src, dst, dt, self.theta)
         elif self.scheme == "BDF2" and self._nrot >= 3:
@@ -140,6 +159,14 @@ class Ensemble(Observed):
     def _record_on(self, series_set):
         series_set.record(self.solver, self.cur, self.t, self._nsteps, self._x, self._member_pars)
 
+    def apply_hook(self):
+        """One application of the attached :class:`~triflow_amd.hooks.ExpressionHook` to the current state
+        of every member, in place, at the ensemble's ``t`` (``tf_hook_apply``)."""
+        if self._program is None:
+            raise RuntimeError("this Ensemble has no ExpressionHook")
+        self._program.update(self.t, self.t, self._x, self._member_pars)
+        self._program.handle.apply(self.cur, self.cur)
+
     def restart(self):
         """Back to the initial state and t = 0 (parameters, hook and factorisation plan stay; a
         device-to-device copy, queued like a step; needs ``nstate >= 3``): long benchmark runs
@@ -162,6 +189,8 @@ class Ensemble(Observed):
     def close(self):
         for series_set in self._observer_sets():
             series_set.close()
+        if self._program is not None:
+            self._program.handle.close()
         self.solver.close()
 
     def state(self):

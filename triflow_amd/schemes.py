@@ -30,29 +30,35 @@ from functools import wraps
 
 import numpy as np
 
-from .device import DirichletHook, null_hook, stepper_for
+from .device import DirichletHook, ExpressionHook, null_hook, stepper_for
 from .tableaux import ERK_TABLEAUX, TABLEAUX
 
 log = logging.getLogger(__name__)
 log.addHandler(logging.NullHandler())
 
-__all__ = ["null_hook", "DirichletHook", "time_stepping", "Theta", "ROW_general", "ROS2",
+__all__ = ["null_hook", "DirichletHook", "ExpressionHook", "time_stepping", "Theta", "ROW_general", "ROS2",
            "ROS3PRw", "ROS3PRL", "RODASPR", "BDF2", "scipy_ode",
            "ERK_general", "SSPRK3", "RK4", "BS23", "DOPRI5"]
 
 
-def _is_device_hook(hook):
+def _is_device_hook(hook, idempotent_only=False):
+    """Is ``hook`` applied on the device?  None, a :class:`DirichletHook` or an :class:`ExpressionHook`
+    (``idempotent_only``: a scheme that hooks its input in place takes a program only if applying it
+    twice is applying it once)."""
+    if isinstance(hook, ExpressionHook):
+        return hook.idempotent or not idempotent_only
     return hook is null_hook or isinstance(hook, DirichletHook) or \
         getattr(hook, "__name__", "") == "null_hook"
 
 
-def _device_step(model, t, fields, pars, hook, launch, dt=None):
+def _device_step(model, t, fields, pars, hook, launch, dt=None, device_hook=None):
     """Common prologue of every scheme: resident source slot (uploading when the
     caller handed over host data), hook at ``t``, one device step into a free
     slot.  ``launch(solver, src, dst)`` issues the kernels; returns
-    ``(new_fields, pars, launch result)``."""
-    if _is_device_hook(hook):
-        if isinstance(hook, DirichletHook):
+    ``(new_fields, pars, launch result)``.  ``device_hook``: the caller's own answer to
+    ``_is_device_hook``."""
+    if _is_device_hook(hook) if device_hook is None else device_hook:
+        if isinstance(hook, (DirichletHook, ExpressionHook)):
             pars = hook.update_pars(t, pars)          # hook(t, ...) may return new parameters
         stepper = stepper_for(model, fields, pars)
         stepper.bind(fields, pars)
@@ -117,6 +123,9 @@ def _fused_trial(scheme, t, fields, dt_, m, pars, hook, ord):
     if desc is None or ord not in (2, np.inf) or not _is_device_hook(hook):
         return None
     if isinstance(hook, DirichletHook) and (hook.time_dependent or hook.parameters is not None):
+        return None
+    if isinstance(hook, ExpressionHook) and (hook.time_dependent or hook.parameters is not None
+                                             or not hook.idempotent):
         return None
     stepper = stepper_for(scheme._model, fields, pars)
     if stepper.nstate < 5 or stepper.solver.nsys != 1:
@@ -552,7 +561,11 @@ class BDF2:
     (a restart, another trajectory) is the backward-Euler form
     ``(I - dt J)(U_{n+1} - U_n) = dt F``.  The history ``U_{n-1}`` lives on the device
     and belongs to this scheme object: several BDF2 objects can step on the same model
-    (they share one ``tf_solver``) without seeing each other's history."""
+    (they share one ``tf_solver``) without seeing each other's history.
+
+    An :class:`ExpressionHook` is applied on the device only if it is idempotent: the step may hook its
+    input in place, and applying a sponge twice there is wrong.  Any other program is used as the callable it
+    is (the generic path: the state goes through the host)."""
 
     _ids = iter(range(1, 2 ** 62))
 
@@ -569,8 +582,9 @@ class BDF2:
             if not any(s is solver for s in self._solvers):
                 self._solvers.append(solver)
             solver.step_bdf2(src, dst, dt, owner=self._owner, continuing=continuing)
-        new, pars, _ = _device_step(self._model, t, fields, pars, hook, launch, dt=dt)
-        if not _is_device_hook(hook):
+        on_device = _is_device_hook(hook, idempotent_only=True)
+        new, pars, _ = _device_step(self._model, t, fields, pars, hook, launch, dt=dt, device_hook=on_device)
+        if not on_device:
             new, _ = hook(t + dt, new, pars)
         try:
             self._last = weakref.ref(new)

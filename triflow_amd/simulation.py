@@ -35,7 +35,7 @@ import numpy as np
 from numpy import isclose
 
 from . import schemes
-from .device import DirichletHook, null_hook, stepper_for
+from .device import DirichletHook, ExpressionHook, null_hook, stepper_for
 from .observers import Observed
 
 __all__ = ["Simulation", "PostProcess", "Stream", "Timer"]
@@ -112,6 +112,12 @@ class Simulation(Observed):
             # (simulation.py:214, schemes.py:145,549); a declarative hook is idempotent, so
             # only its parameter update is taken here and the fields stay on the GPU
             pars = self._hook.update_pars(t, pars)
+        elif isinstance(self._hook, ExpressionHook) and not self._on_host():
+            # an idempotent program as above; any other one is applied here as well (a sponge applied once
+            # where the reference applies it three times gives other bits), on the device
+            pars = self._hook.update_pars(t, pars)
+            if not self._hook.idempotent:
+                fields = stepper_for(self.model, fields, pars).apply_hook(self._hook, t, fields, pars)
         else:
             fields, pars = self._hook(t, fields, pars)
         self.dt = (self.tmax - t if self.tmax and (t + self.dt >= self.tmax) else self.dt)
@@ -123,6 +129,16 @@ class Simulation(Observed):
         self._last_timestamp = self._actual_timestamp
         self._actual_timestamp = datetime.datetime.now()
         return t, fields, pars
+
+    def _on_host(self):
+        """The scheme is none of this package's device schemes (``scipy_ode``, a host solver): an
+        :class:`ExpressionHook` is then the callable it is."""
+        scheme = getattr(self._scheme, "__wrapped__", self._scheme)
+        if isinstance(scheme, schemes.Theta):
+            return scheme._solver is not None
+        if isinstance(scheme, schemes.BDF2):
+            return not self._hook.idempotent
+        return not isinstance(scheme, schemes.ROW_general)
 
     def compute(self):
         """Generator yielding ``(t, fields)`` after every ``dt``."""

@@ -291,9 +291,9 @@ const char* tf_kernel_name(int32_t kernel);
  * (np.trapz; periodic: dx * sum), 3 max, 4 min, 5 argmax, 6 argmin (x of the first extremal node);
  * NaN as numpy has it.  nconst: host constants of the probe expressions (codegen spec
  * "host_consts"), set per system by tf_probe_set_consts.  A record is queued on the solver's
- * stream (no host wait) and writes one row [nsys][nprobe] into a device ring of `capacity` rows;
- * a record that finds the ring full first copies it to host memory (one wait per `capacity`
- * records).  A probe belongs to its solver: destroy it first. */
+ * stream (no host wait) and writes one row [nsys][nprobe] into a device ring of `capacity` rows,
+ * which the host counts; a record that finds the ring full first copies it to host memory (one wait
+ * per `capacity` records).  A probe belongs to its solver: destroy it first. */
 typedef struct tf_probe tf_probe;
 int tf_probe_create(tf_solver*, const void* code_object, size_t code_size, int32_t nprobe,
                     const int32_t* kinds, int32_t nconst, int32_t capacity, tf_probe** out);
@@ -317,7 +317,8 @@ int tf_probe_pending(tf_probe*, int64_t* rows);
  * the rows of the recorder's device ring (>= 2: two halves).
  * Column j of a recorder is its expression pooled over nodes start + j*step ...
  * min(start + (j+1)*step, stop) - 1; NaN as numpy has it; the mean's sum is added in a fixed order.
- * A record is queued on the solver's stream (no host wait) and writes one row [nsys][ncols]; a half
+ * A record is queued on the solver's stream (no host wait) and writes one row [nsys][ncols], which the
+ * host counts; a half
  * of the ring that is full is copied to page-locked host memory by a stream of the recorder's own
  * while the records go on into the other half.  A recorder belongs to its solver: destroy it first. */
 typedef struct tf_record tf_record;

@@ -42,14 +42,16 @@ def build():
             raise RuntimeError("ring harness build failed:\n" + res.stderr[-4000:])
         os.replace(tmp, so)
     lib = C.CDLL(so)
-    lib.ring_host_create.restype = C.c_void_p
-    lib.ring_host_create.argtypes = [C.c_int, C.c_int]
-    lib.ring_host_destroy.argtypes = [C.c_void_p]
-    lib.ring_host_push.argtypes = [C.c_void_p, C.c_double]
-    lib.ring_host_fetch.restype = C.c_int64
-    lib.ring_host_fetch.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int64]
-    lib.ring_host_pending.restype = C.c_int64
-    lib.ring_host_pending.argtypes = [C.c_void_p]
+    for prefix in ("ring_host_", "half_host_"):
+        fn = lambda name: getattr(lib, prefix + name)
+        fn("create").restype = C.c_void_p
+        fn("create").argtypes = [C.c_int, C.c_int]
+        fn("destroy").argtypes = [C.c_void_p]
+        fn("push").argtypes = [C.c_void_p, C.c_double]
+        fn("fetch").restype = C.c_int64
+        fn("fetch").argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int64]
+        fn("pending").restype = C.c_int64
+        fn("pending").argtypes = [C.c_void_p]
     return lib
 
 
@@ -57,23 +59,36 @@ class Ring:
     """A RowRing of ``capacity`` rows of ``width`` doubles.  ``push(tag)`` records the row ``tag + 0.25 * j``
     and returns the index the ring handed out; ``fetch(max_rows)`` returns ``[rows][width]``."""
 
+    prefix = "ring_host_"
+    keeps_count = False                # a fetch empties the ring: the next row is 0 again
+
     def __init__(self, lib, capacity, width):
         self.lib, self.width = lib, width
-        self.handle = C.c_void_p(lib.ring_host_create(capacity, width))
+        self.handle = C.c_void_p(self._fn("create")(capacity, width))
+
+    def _fn(self, name):
+        return getattr(self.lib, self.prefix + name)
 
     def close(self):
-        self.lib.ring_host_destroy(self.handle)
+        self._fn("destroy")(self.handle)
         self.handle = None
 
     def push(self, tag):
-        return self.lib.ring_host_push(self.handle, float(tag))
+        return self._fn("push")(self.handle, float(tag))
 
     def pending(self):
-        return self.lib.ring_host_pending(self.handle)
+        return self._fn("pending")(self.handle)
 
     def fetch(self, max_rows):
         out = np.full((max(max_rows, 1), self.width), -7.25)
-        n = self.lib.ring_host_fetch(self.handle, out.ctypes.data_as(C.POINTER(C.c_double)), max_rows)
+        n = self._fn("fetch")(self.handle, out.ctypes.data_as(C.POINTER(C.c_double)), max_rows)
         assert 0 <= n <= max(max_rows, 0)
         assert (out[n:] == -7.25).all(), "fetch wrote past the rows it reported"
         return out[:n]
+
+
+class HalfRing(Ring):
+    """A HalfRing of ``capacity`` rows (two halves of ``capacity // 2``) of ``width`` doubles; as ``Ring``."""
+
+    prefix = "half_host_"
+    keeps_count = True                 # the index is that of all the rows pushed, modulo the capacity

@@ -218,6 +218,49 @@ def test_ensemble_probes_per_member():
     ens.close()
 
 
+def test_ring_of_four_rows_gives_the_rows_of_the_default_ring(monkeypatch):
+    """50 rows through a ring of 4: the host counts the row, the full ring is drained twelve times on the
+    way, and times and values are the bytes of the same run with the default ring (which never fills)."""
+    default = probed_run(film_inputs(4096), FILM_PROBES, 49)
+    monkeypatch.setattr(probes, "DEFAULT_CAPACITY", 4)
+    small = probed_run(film_inputs(4096), FILM_PROBES, 49)
+    for p in FILM_PROBES:
+        assert small[p[0]][1].shape == (50,)
+        assert small[p[0]][0].tobytes() == default[p[0]][0].tobytes(), p[0]
+        assert small[p[0]][1].tobytes() == default[p[0]][1].tobytes(), p[0]
+
+
+def ensemble_run(nsys, steps):
+    name, fields, pars, dt = film_inputs(4096)
+    model = model_of(name)
+    member_pars = dict(pars)
+    member_pars["We"] = np.linspace(.005, .02, nsys)
+    member_pars["c"] = np.linspace(.5, 1.5, nsys)
+    fdict = {k: np.tile(fields[k], (nsys, 1)) for k in model._dep_vars}
+    ens = Ensemble(model, fields["x"], fdict, member_pars, periodic=True, scheme="ROS2")
+    for pname, expr, kind in FILM_PROBES:
+        ens.add_probe(pname, expr, reduce=kind)
+    for _ in range(steps):
+        ens.step(dt)
+    got = dict(ens.probes)
+    ens.close()
+    return got
+
+
+def test_ensemble_ring_of_four_rows_gives_the_rows_of_the_default_ring(monkeypatch):
+    """Eight members, 10 rows [nsys][nprobe] through a ring of 4 (a workgroup of tfk_probe_final per
+    member): byte-equal to the default ring, member by member -- a wrong row index or row stride shows."""
+    default = ensemble_run(8, 9)
+    monkeypatch.setattr(probes, "DEFAULT_CAPACITY", 4)
+    small = ensemble_run(8, 9)
+    for p in FILM_PROBES:
+        assert small[p[0]][1].shape == (10, 8)
+        assert np.asarray(small[p[0]][0]).tobytes() == np.asarray(default[p[0]][0]).tobytes(), p[0]
+        assert small[p[0]][1].tobytes() == default[p[0]][1].tobytes(), p[0]
+    # (the members differ: a row that landed in another member's place would show)
+    assert len({small["crest"][1][-1, e] for e in range(8)}) == 8
+
+
 def test_host_constants_follow_changed_parameters():
     """A DirichletHook that returns new parameters every step: the probes' host constants (We**3 of
     "slope") are refreshed with the parameters the step was bound with."""

@@ -214,7 +214,7 @@ def test_adaptive_steps_record_every_accepted_step():
 
 def test_small_grid_with_graph_replay():
     """Config 3 at 20 000 nodes (graph replay on by default below 5e4 nodes): a replayed step must not
-    freeze the cursor or the slot."""
+    freeze the row or the slot (the record launches are outside the captured step)."""
     inputs = film_inputs(20_000)
     steps = 30
     got = recorded_run(inputs, FILM_RECS[:3], steps)

@@ -367,8 +367,8 @@ struct TfNodeArgs {
 // Device probes (tf_probe.h, tf_rt_probe.cpp): reductions of model expressions over the nodes of every
 // system, evaluated on a resident state slot.  tfk_probe_partial: grid (nsys * nblk, nseg), one thread per
 // segment of TF_PROBE_SEG nodes of a level-1 chunk, one partial per workgroup, probe and system;
-// tfk_probe_final: grid (nsys), reduces the partials of its system in a fixed order and writes one row of
-// the ring.  Reductions (codegen.PROBE_REDUCTIONS: same order):
+// tfk_probe_final: grid (nsys), reduces the partials of its system in a fixed order and writes row `row`
+// of the ring.  Reductions (codegen.PROBE_REDUCTIONS: same order):
 #define TF_PROBE_SUM 0
 #define TF_PROBE_MEAN 1
 #define TF_PROBE_INTEGRAL 2
@@ -385,15 +385,15 @@ struct TfProbeArgs : TfNodeArgs {
     double* ends;                  // [nsys][nprobe][2]: f at natural nodes 0 and N-1 (integral)
     int nblk;                      // workgroups of tfk_probe_partial per system and segment row
     int nseg;                      // segments of TF_PROBE_SEG nodes per chunk
+    int row;                       // row of the ring this launch writes (by value: the host counts)
     int capacity;                  // rows of the ring
-    int* cursor;                   // [0]: next row of the ring, [1]: systems done with the current row
     double* ring;                  // [capacity][nsys][nprobe]
 };
 
 // Device recorders (tf_record.h, tf_rt_record.cpp): decimated space-time series of model expressions.
 // Column j of a recorder covers the bin of natural nodes start + j*step ... min(start + (j+1)*step, stop) - 1
 // of every system; tfk_record evaluates expression `which` of the record block on a resident state slot
-// and stores one row [nsys][ncols] of the recorder's ring.  Pools:
+// and stores row `row`, [nsys][ncols], of the recorder's ring.  Pools:
 #define TF_REC_SAMPLE 0            // the expression at the bin's first node
 #define TF_REC_MAX 1               // over the bin's nodes, NaN as numpy has it (tf_probe_combine)
 #define TF_REC_MIN 2
@@ -408,8 +408,8 @@ struct TfRecordArgs : TfNodeArgs {
     int split;                     // threads per bin
     int part;                      // nodes per thread = ceil(step / split)
     int nblk;                      // workgroups per system
+    int row;                       // row of the ring this launch writes (by value: the host counts, and wraps)
     int capacity;                  // rows of the ring (both halves)
-    int* cursor;                   // [0]: next row of the ring (wraps at capacity), [1]: workgroups done with it
     double* ring;                  // [capacity][nsys][ncols]
 };
 
@@ -541,7 +541,7 @@ struct TfHookArgs : TfNodeArgs {
 static_assert(sizeof(TfHookArgs) == 128, "TfHookArgs changed its layout");
 static_assert(sizeof(TfHistArgs) == 160, "TfHistArgs changed its layout");
 static_assert(sizeof(TfNodeArgs) == 96, "TfNodeArgs changed its layout");
-static_assert(sizeof(TfProbeArgs) == 144, "TfProbeArgs changed its layout");
+static_assert(sizeof(TfProbeArgs) == 136, "TfProbeArgs changed its layout");
 static_assert(sizeof(TfRecordArgs) == 152, "TfRecordArgs changed its layout");
 static_assert(sizeof(TfStatArgs) == 136, "TfStatArgs changed its layout");
 static_assert(sizeof(TfSpectrumArgs) == 144, "TfSpectrumArgs changed its layout");

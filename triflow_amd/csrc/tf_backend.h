@@ -95,10 +95,10 @@ void event_destroy(Event* e);
 void event_record(Event* e, Stream* s);
 float event_elapsed_ms(Event* a, Event* b);   // both completed
 
-// Copies that overlap the stream they come from (the recorder ring, tf_rt_record.cpp): page-locked host
+// Copies that overlap the stream they come from (the recorders' ring: HalfRing, tf_solver.h): page-locked host
 // memory, a copy that is only queued, a stream that waits for an event of another stream without the
 // host waiting, and the host waiting for one event.  A back end without them need not define any:
-// tf_rt_record.cpp holds weak definitions in terms of the calls above (pageable memory, d2h, no overlap).
+// tf_solver.h holds weak definitions in terms of the calls above (pageable memory, d2h, no overlap).
 void* host_alloc(size_t bytes);
 void host_free(void* p);
 void d2h_async(void* dst, const void* src, size_t bytes, Stream* s);

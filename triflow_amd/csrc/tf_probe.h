@@ -9,8 +9,8 @@
 //
 // The reduction algebra and the walk of one thread along its chunk, on the node window that the
 // probes share with the other observers (tf_node.h), are what the host harness of the test suite
-// (tests/probe_host/) also compiles with g++; the kernels, with the shuffle / LDS trees and the ring
-// hand-over, are at the end of the file.
+// (tests/probe_host/) also compiles with g++; the kernels, with the shuffle / LDS trees and the store
+// into the ring, are at the end of the file.
 #pragma once
 #include "tf_node.h"
 
@@ -137,13 +137,12 @@ extern "C" __global__ void __launch_bounds__(256) tfk_probe_partial(TfProbeArgs 
 }
 // grid (nsys), 256 threads: wavefront w reduces probes w, w + 4, ... of one system -- the
 // partials in a fixed order, strided over the lanes, then the shuffle tree -- and lane 0 writes the finished
-// value into row cursor[0] of the ring.  The row cursor lives in device memory: every workgroup reads it,
-// and the last of them to be done with the row (an integer counter) advances it -- a replayed launch
-// writes the next row, not the one it was captured with.
+// value into row a.row of the ring.  The row comes by value, from the host's count of the rows: the
+// launch is queued on the solver's stream between the steps, never inside a captured graph (a replay
+// would write every row where it was captured).
 extern "C" __global__ void __launch_bounds__(256) tfk_probe_final(TfProbeArgs a) {
     const int e = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const TfLayout& L = a.L;
-    const int row = *(volatile int*)&a.cursor[0];
     const int nb = a.nblk * a.nseg;
     for (int k = wave; k < TF_NPROBE; k += 4) {
         const int kind = tf_probe_kind[k];
@@ -174,15 +173,7 @@ extern "C" __global__ void __launch_bounds__(256) tfk_probe_final(TfProbeArgs a)
             const double f0 = kind == TF_PROBE_INTEGRAL ? end[0] : 0.0;
             const double fN1 = kind == TF_PROBE_INTEGRAL ? end[1] : 0.0;
             const double val = tf_probe_finish(kind, r, L.N, L.periodic, a.dx[e], f0, fN1, xnode);
-            if (row < a.capacity) a.ring[((int64_t)row * L.nsys + e) * TF_NPROBE + k] = val;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        if (atomicAdd(&a.cursor[1], 1) == L.nsys - 1) {
-            atomicExch(&a.cursor[1], 0);
-            atomicExch(&a.cursor[0], row < a.capacity ? row + 1 : row);
+            if (a.row >= 0 && a.row < a.capacity) a.ring[((int64_t)a.row * L.nsys + e) * TF_NPROBE + k] = val;
         }
     }
 }

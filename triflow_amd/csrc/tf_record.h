@@ -65,14 +65,13 @@ TF_DEVICE double tf_record_finish(const TfRecordArgs& a, int j, const double* pa
 // walks `part` nodes of it (at most 8 where the bin allows: the threads of a wavefront then read a few
 // whole rows of neighbouring chunks, and a bin of 64 nodes keeps 8 threads busy instead of one); the
 // parts meet in LDS and the first TF_REC_BLOCK / split threads combine them in part order and store the
-// columns of the workgroup side by side in row cursor[0] of the ring.  The row cursor lives in device
-// memory, as the probes' does: the last workgroup to be done with the row (an integer counter) moves it
-// on, wrapping at the ring's capacity -- a replayed launch writes the next row.  No floating-point atomics.
+// columns of the workgroup side by side in row a.row of the ring.  The row comes by value, as the probes'
+// does, from the host's count of the rows, which wraps at the ring's capacity: the launch is queued on the
+// solver's stream between the steps, never inside a captured graph.  No atomics.
 extern "C" __global__ void __launch_bounds__(TF_REC_BLOCK) tfk_record(TfRecordArgs a) {
     __shared__ double parts[TF_REC_BLOCK];
     const int e = blockIdx.x / a.nblk, blk = blockIdx.x - e * a.nblk;
     const int cpb = TF_REC_BLOCK / a.split;
-    const int row = *(volatile int*)&a.cursor[0];
     const int c = threadIdx.x / a.split, s = threadIdx.x - c * a.split;
     const int j = blk * cpb + c;
     double v = 0.0;
@@ -80,15 +79,7 @@ extern "C" __global__ void __launch_bounds__(TF_REC_BLOCK) tfk_record(TfRecordAr
     parts[threadIdx.x] = v;
     __syncthreads();
     const int jj = blk * cpb + threadIdx.x;
-    if (threadIdx.x < cpb && jj < a.ncols && row >= 0 && row < a.capacity)
-        a.ring[((int64_t)row * a.L.nsys + e) * a.ncols + jj] = tf_record_finish(a, jj, parts + threadIdx.x * a.split);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        if (atomicAdd(&a.cursor[1], 1) == (int)gridDim.x - 1) {
-            atomicExch(&a.cursor[1], 0);
-            atomicExch(&a.cursor[0], row + 1 < a.capacity ? row + 1 : 0);
-        }
-    }
+    if (threadIdx.x < cpb && jj < a.ncols && a.row >= 0 && a.row < a.capacity)
+        a.ring[((int64_t)a.row * a.L.nsys + e) * a.ncols + jj] = tf_record_finish(a, jj, parts + threadIdx.x * a.split);
 }
 #endif

@@ -32,18 +32,14 @@ int tf_stat_create(tf_solver* s, const void* code_object, size_t code_size, int3
     require(nstat >= 1 && nstat <= 64, "tf_stat_create: 1 ... 64 statistics");
     require(nconst >= 0, "tf_stat_create: bad constant count");
     std::unique_ptr<tf_stat> p(new tf_stat());
-    // The expressions of the block are numbered in the order the statistics first use them
-    // (StatisticSet.expressions): a statistic names one that an earlier statistic named, or the next one.
-    // So no index passes that is not a case of tf_eval_stat in a block lowered from the same set.
     int nexpr = 0;
     for (int k = 0; k < nstat; ++k) {
         p->accs.emplace_back(new Acc());
         Acc& a = *p->accs[k];
         a.expr = geometry[2 * k];
         a.kind = geometry[2 * k + 1];
-        require(a.expr >= 0 && a.expr <= nexpr,
-                "tf_stat_create: expressions are numbered in the order the statistics first use them");
-        nexpr = std::max(nexpr, a.expr + 1);
+        tf_observer::require_numbered_in_order(
+            a.expr, nexpr, "tf_stat_create: expressions are numbered in the order the statistics first use them");
         require(a.kind >= 0 && a.kind < TF_STAT_KINDS, "tf_stat_create: unknown kind of statistic");
         a.planes = tf_stat_planes(a.kind);
     }

@@ -641,8 +641,8 @@ struct tf_solver {
 // An observer is one more code object of the solver's model -- the model's generated body, a generated
 // block of expressions and the header of the observer's kind -- that holds the kernels of that kind alone;
 // they are launched on the solver's stream, on one of its state slots.  Here: the inputs of the node core
-// (TfNodeArgs; csrc/tf_node.h) and the launch.  Rings and copies are the observer's own
-// (the spectra, the extrema and the histograms: RowRing, below).
+// (TfNodeArgs; csrc/tf_node.h) and the launch.  The rings are below: the host counts the rows of every
+// kind (the probes, the spectra, the extrema and the histograms: RowRing; the recorders: HalfRing).
 struct tf_observer {
     tf_solver* solver = nullptr;
     tfb::Module* module = nullptr;
@@ -713,8 +713,8 @@ struct tf_observer {
     }
 };
 
-// The ring of rows in device memory of an observer that writes one row per record (spectra, extrema,
-// histograms).  The host counts the rows and hands the row index to the kernels by value: nothing of the
+// The ring of rows in device memory of an observer that writes one row per record (probes, spectra,
+// extrema, histograms).  The host counts the rows and hands the row index to the kernels by value: nothing of the
 // ring's state lives on the device, and a record never waits.  The host waits only when the ring is full
 // (one copy of all of it before the next record) and when the caller fetches.  A record is
 //     row = next_row(stream);  build the arguments;  queue the launches;  ++on_device;
@@ -751,4 +751,141 @@ struct RowRing {
         *nrows = n;
     }
     int64_t pending() const { return on_device + (int64_t)(rows.size() / row); }
+};
+
+// Back ends without asynchronous copies (tf_backend.h): the same calls without the overlap.
+namespace tfb {
+__attribute__((weak)) void* host_alloc(size_t bytes) { return std::malloc(bytes ? bytes : 8); }
+__attribute__((weak)) void host_free(void* p) { std::free(p); }
+__attribute__((weak)) void d2h_async(void* dst, const void* src, size_t bytes, Stream* s) { d2h(dst, src, bytes, s); }
+__attribute__((weak)) void stream_wait_event(Stream*, Event*) {}
+__attribute__((weak)) void event_sync(Event*) {}
+}  // namespace tfb
+
+// The ring of rows in device memory of an observer whose rows are large (the recorders): two halves.  As in
+// RowRing the host counts the rows and the kernel takes the row index by value, and rows taken from the
+// device wait in `rows` for the caller's fetch.  What it adds: a full half does not stop the records.  An
+// event on the solver's stream lets a copy stream move the half into a page-locked buffer of its own while
+// the records go on into the other half; before a half is written again the solver's stream waits (a
+// stream-side wait) for the copy of it.  The host waits in fetch, and where the copy of a half needs a
+// page-locked buffer whose rows it has not taken yet -- a copy queued two halves earlier.  A record is
+//     row = begin_row(stream);  build the arguments;  queue the launch;  end_row(stream, copy);
+struct HalfRing {
+    int half = 1;                              // rows of one half
+    size_t row = 0;                            // doubles of one row
+    DevBuf dev;                                // 2 * half rows
+    double* pinned[2] = {nullptr, nullptr};
+    tfb::Event* full[2] = {nullptr, nullptr};  // on the solver's stream: the rows of half h are written
+    tfb::Event* copied[2] = {nullptr, nullptr};   // on the copy stream: half h is in pinned[h]
+    int64_t head = 0;                          // rows recorded so far (row head % (2 * half) is next)
+    int lo[2] = {0, 0};                        // rows at the start of half h that were fetched from a part-filled half
+    int flying[2] = {0, 0};                    // rows of pinned[h] (copied or on their way) not taken yet
+    bool guard[2] = {false, false};            // the next write into half h has to wait for copied[h]
+    std::vector<double> rows;                  // taken, not fetched
+
+    HalfRing() = default;
+    HalfRing(const HalfRing&) = delete;
+    HalfRing& operator=(const HalfRing&) = delete;
+    ~HalfRing() { release(); }
+    void alloc(int64_t& total) {
+        dev.alloc(2 * (size_t)half * row, total);
+        for (int h = 0; h < 2; ++h) {
+            pinned[h] = (double*)tfb::host_alloc((size_t)half * row * sizeof(double));
+            full[h] = tfb::event_create();
+            copied[h] = tfb::event_create();
+        }
+    }
+    // (the owner has waited for the copy stream)
+    void release() {
+        for (int h = 0; h < 2; ++h) {
+            tfb::host_free(pinned[h]);
+            tfb::event_destroy(full[h]);
+            tfb::event_destroy(copied[h]);
+            pinned[h] = nullptr;
+            full[h] = copied[h] = nullptr;
+        }
+        dev.release();
+    }
+    int cur() const { return (int)((head / half) % 2); }           // the half the next record writes
+    int fill() const { return (int)(head % half); }                // rows of it that are written
+    double* rows_of(int h, int r) const { return dev.p + ((size_t)h * half + r) * row; }
+
+    // rows [from, from + n) of half h to pinned[h], behind what the solver's stream has queued so far
+    void queue_copy(int h, int from, int n, tfb::Stream* stream, tfb::Stream* copy) {
+        tfb::event_record(full[h], stream);
+        tfb::stream_wait_event(copy, full[h]);
+        tfb::d2h_async(pinned[h], rows_of(h, from), (size_t)n * row * sizeof(double), copy);
+        tfb::event_record(copied[h], copy);
+        flying[h] = n;
+    }
+    // the rows of pinned[h] to `rows` (waits for their copy)
+    void take(int h) {
+        if (flying[h] == 0) return;
+        tfb::event_sync(copied[h]);
+        rows.insert(rows.end(), pinned[h], pinned[h] + (size_t)flying[h] * row);
+        flying[h] = 0;
+    }
+    // every recorded row to `rows`, oldest first
+    void drain(tfb::Stream* stream, tfb::Stream* copy) {
+        const int h = cur();
+        take(h);                               // (the copy of this half's last round is the older one)
+        take(1 - h);
+        if (fill() > lo[h]) {
+            queue_copy(h, lo[h], fill() - lo[h], stream, copy);
+            take(h);
+            lo[h] = fill();
+        }
+    }
+    // the row the next record writes; the first row of a half that was copied: after its copy
+    int begin_row(tfb::Stream* stream) {
+        const int h = cur();
+        if (fill() == 0 && guard[h]) {
+            tfb::stream_wait_event(stream, copied[h]);
+            guard[h] = false;
+        }
+        return (int)(head % (2 * half));
+    }
+    // the launch is queued; a half that is full now: its copy, while the other half fills
+    void end_row(tfb::Stream* stream, tfb::Stream* copy) {
+        const int h = cur();
+        ++head;
+        if (fill() != 0) return;
+        take(h);                               // (rows of this half's last round still in pinned[h])
+        queue_copy(h, lo[h], half - lo[h], stream, copy);
+        lo[h] = 0;
+        guard[h] = true;
+    }
+    int64_t pending() const { return (int64_t)(rows.size() / row) + flying[0] + flying[1] + fill() - lo[cur()]; }
+    // the oldest rows, max_rows at most, to out; what was not copied stays for the next fetch
+    void fetch(tfb::Stream* stream, tfb::Stream* copy, double* out, int64_t max_rows, int64_t* nrows) {
+        if (max_rows >= pending()) {
+            // everything fits: the rows of the page-locked buffers go straight to the caller, oldest first
+            const int h = cur();
+            double* at = out;
+            auto put = [&](const double* src, size_t n) { if (n) std::memcpy(at, src, n * row * sizeof(double)); at += n * row; };
+            put(rows.data(), rows.size() / row);
+            rows.clear();
+            for (int hh : {h, 1 - h}) {        // (the copy of this half's last round is the older one)
+                if (flying[hh] == 0) continue;
+                tfb::event_sync(copied[hh]);
+                put(pinned[hh], (size_t)flying[hh]);
+                flying[hh] = 0;
+            }
+            if (fill() > lo[h]) {
+                queue_copy(h, lo[h], fill() - lo[h], stream, copy);
+                tfb::event_sync(copied[h]);
+                put(pinned[h], (size_t)flying[h]);
+                flying[h] = 0;
+                lo[h] = fill();
+            }
+            *nrows = (int64_t)((at - out) / (int64_t)row);
+            return;
+        }
+        drain(stream, copy);
+        const int64_t have = (int64_t)(rows.size() / row);
+        const int64_t n = std::min<int64_t>(have, std::max<int64_t>(max_rows, 0));
+        if (n) std::memcpy(out, rows.data(), (size_t)n * row * sizeof(double));
+        rows.erase(rows.begin(), rows.begin() + (size_t)n * row);
+        *nrows = n;
+    }
 };
